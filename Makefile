@@ -18,7 +18,7 @@ test-gpu:
 	$(PY) -m pytest tests -m gpu -q
 
 bench:
-	$(PY) bench.py
+	$(PY) bench.py --full
 
 suite:
 	$(PY) -m vgpu.bench.suite

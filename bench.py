@@ -25,9 +25,16 @@ the job's ms_per_step is the MAX over ranks, and `value` is total images over
 all pods on all GPUs divided by that wall time (weak scaling: per-GPU work is
 fixed as N grows).
 
+A plain run does only that: set up, warm up, time the K steps, print the
+result line.  ``--dump-outputs DIR`` adds one file per pod with the output of
+its last timed step (model and input are seeded per pod, so two builds can be
+compared output for output).  ``--full`` adds the checks that take runs of
+their own after the timed window: the VRAM-cap probe of every pod (`vram_cap`
+in the JSON: 1 GiB blocks until the cap refuses) and the RCCL check below.
+
 The ranks coordinate over gloo (they never touch a GPU).  Before GO a
 preflight checks the placement: N distinct devices, one share board (device
-uuid) per GPU, one shared region per pod.  With N > 1, after the timed window
+uuid) per GPU, one shared region per pod.  With ``--full`` and N > 1, after the timed window
 pod 0 of every GPU joins one RCCL process group and all-reduces 64 MiB
 (`rccl_check` in the JSON): RCCL kernels under the shim's limiter and IPC
 buffers across pods.  Each of those pods sees ONE GPU, so RCCL cannot map its
@@ -47,6 +54,7 @@ import time
 
 METRIC = "aggregate ai-benchmark score, N pods sharing 1 MI355X; VRAM-cap accuracy"
 BASELINE_VGPU_R50_INF = 141.2  # images/s, ResNet-V2-50 inference, vGPU-device-plugin
+DUMP_BYTES = 60 << 20  # --dump-outputs: all pods of all ranks together stay under 64 MB
 
 
 def log(msg: str) -> None:
@@ -101,7 +109,15 @@ def make_parser() -> argparse.ArgumentParser:
     ap.add_argument("--pool-concurrency", type=int, default=None,
                     help="device plugin --pool-concurrency: temporal-pool members of a GPU running at once "
                          "(0 = all; default: the plugin's)")
-    ap.add_argument("--no-cap-probe", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks that are not part of the headline figure, after the timed "
+                         "window: the VRAM-cap probe of every pod (`vram_cap`) and, with N > 1, the RCCL "
+                         "all-reduce among one pod per GPU (`rccl_check`)")
+    ap.add_argument("--no-cap-probe", action="store_true", help="with --full: skip the VRAM-cap probe")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps every pod writes what its last timed step returned (logits; "
+                         "the loss of a training workload) as DIR/[rank<r>_]pod<i>_<name>.npy, float32, "
+                         "at most 64 MB in all (a larger output as a fixed, seeded sample)")
     ap.add_argument("--warmup-seconds", type=float, default=0.0,
                     help="pods keep warming up (untimed) until this long has passed")
     ap.add_argument("--decide-timeout", type=float, default=30.0,
@@ -332,6 +348,8 @@ def main(argv=None) -> int:
         args.no_shim = True
         args.no_cap_probe = True
     if args.pod_gpus > 0:
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs writes the headline pods' outputs; --pod-gpus runs none")
         sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
         return pod_gpus_main(args)
 
@@ -369,7 +387,9 @@ def main(argv=None) -> int:
                      extra_env=dict(pol_env)) for i in range(args.pods)]
     log(f"rank {rank}/{world}: launching {args.pods} pods of {w.name} (test {w.test_id}) on device {device}")
     pods = launch_pods(specs, device, steps=args.steps, warmup=args.warmup, shim=not args.no_shim,
-                       graph=not args.no_graph, cap_probe=not args.no_cap_probe,
+                       graph=not args.no_graph, cap_probe=args.full and not args.no_cap_probe,
+                       dump_outputs=args.dump_outputs, dump_prefix=f"rank{rank}_" if world > 1 else "",
+                       dump_bytes=DUMP_BYTES // (args.pods * world),
                        find=not args.no_find, hw_queues=args.hw_queues or None,
                        fused=not args.no_fused, conv=args.conv, cu_share=args.cu_share,
                        oversubscribe=args.oversubscribe, memory_scaling=args.memory_scaling,
@@ -400,7 +420,9 @@ def main(argv=None) -> int:
         wall = t_end - t_start
         final_cus = [region_cus(p.region) for p in pods]  # CUs each pod ends on (auto policy may move it)
         rccl = None
-        if pg and pods and distinct:
+        if not args.full:
+            pass  # a plain run ends with the timed window
+        elif pg and pods and distinct:
             rccl = rccl_check(pg, rank, world, pods[0], log)
         elif pg:
             rccl = {"skipped": "ranks share a GPU (rehearsal): RCCL runs one rank per GPU"}
@@ -486,9 +508,11 @@ def main(argv=None) -> int:
             "per_pod_occ_charged_ms": [(p.done.get("share") or {}).get("occ_charged_ms") for p in pods],
             "per_pod_host_pid_src": [(p.done.get("share") or {}).get("host_pid_src") for p in pods],
             "per_pod_decide_wait_s": [((p.ready or {}).get("decide") or {}).get("waited_s") for p in pods],
+            "full": args.full,  # vram_cap and rccl_check are measured only with --full
             "vram_cap": cap,
             "placement": placement,
             "rccl_check": rccl,
+            "dumped_outputs": [p.done.get("dumped") for p in pods] if args.dump_outputs else None,
         }
         print(json.dumps(res), flush=True)
     if pg:

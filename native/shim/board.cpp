@@ -46,8 +46,17 @@ bool lock(vgpu_board_t* b) {
 
 void unlock(vgpu_board_t* b) { pthread_mutex_unlock(&b->lock.m); }
 
+// ns since a slot's heartbeat.  Owners refresh it without the board lock
+// (board_heartbeat), so it may be later than a `now` read just before: that
+// is age 0, not a wrapped-around huge one (which made a live slot look stale
+// and let the concurrency gate admit one runner too many).
+uint64_t hb_age(const vgpu_board_slot_t& s, uint64_t now) {
+  const uint64_t hb = s.heartbeat_ns;
+  return now > hb ? now - hb : 0;
+}
+
 bool live(const vgpu_board_slot_t& s, uint64_t now) {
-  return s.pid != 0 && s.active && now - s.heartbeat_ns < VGPU_BOARD_STALE_NS;
+  return s.pid != 0 && s.active && hb_age(s, now) < VGPU_BOARD_STALE_NS;
 }
 
 // Advance virtual time to `now` at the rate set by the active count of the
@@ -120,7 +129,7 @@ int board_claim(vgpu_board_t* b, int pid, int host_pid, int limit_pct) {
   for (int i = 0; i < VGPU_BOARD_SLOTS && got < 0; ++i) {
     vgpu_board_slot_t& s = b->slot[i];
     // free, or abandoned (no heartbeat for 10 x the stale interval)
-    if (s.pid == 0 || now - s.heartbeat_ns > 10 * VGPU_BOARD_STALE_NS) got = i;
+    if (s.pid == 0 || hb_age(s, now) > 10 * VGPU_BOARD_STALE_NS) got = i;
   }
   if (got >= 0) {
     vgpu_board_slot_t& s = b->slot[got];
@@ -199,7 +208,7 @@ double board_entitlement(vgpu_board_t* b, int slot) {
 
 namespace {
 bool fresh(const vgpu_board_slot_t& s, uint64_t now) {
-  return s.pid != 0 && now - s.heartbeat_ns < VGPU_BOARD_STALE_NS;
+  return s.pid != 0 && hb_age(s, now) < VGPU_BOARD_STALE_NS;
 }
 }  // namespace
 

@@ -36,7 +36,7 @@ for s in "${STAGES[@]}"; do
     tests) step pytest_gpu 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread -p no:cacheprovider
            rc=$?; ok_or_testfail $rc || exit $rc ;;
     smoke) step smoke 600 python -c "import __graft_entry__ as g; g.smoke()" || exit 1 ;;
-    bench) step bench 900 python bench.py || exit 1
+    bench) step bench 900 python bench.py --full || exit 1
            grep '^{' "$OUT/bench.log" | tail -1 > "$OUT/bench.json" ;;
     excl)  step bench_excl 600 python bench.py --pods 1 --gpucores 100 --gpumem 0 --no-cap-probe || exit 1 ;;
     conv)  step convnative 600 python scripts/convnative.py || exit 1 ;;

@@ -30,13 +30,52 @@ def test_bench_single_rank_cpu():
     assert len(d["per_pod_images_s"]) == 2
 
 
+def test_bench_dump_outputs_repeatable_and_plain_run_is_lean(tmp_path):
+    """--dump-outputs writes one float32 array per pod, the same from run to
+    run (seeded inputs); a run without --full leaves the post-timing checks out."""
+    import numpy as np
+    got = []
+    for name in ("a", "b"):
+        r = subprocess.run([sys.executable, "bench.py", "--cpu-smoke", "--steps", "3", "--warmup", "1", "--pods", "2",
+                            "--dump-outputs", str(tmp_path / name)], cwd=REPO, capture_output=True, text=True,
+                           timeout=300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert d["steps"] == 3 and d["ms_per_step"] > 0
+        assert d["full"] is False and d["vram_cap"] == [] and d["rccl_check"] is None
+        files = sorted(os.listdir(tmp_path / name))
+        assert files == ["pod0_output.npy", "pod1_output.npy"]
+        assert [x["file"] for x in d["dumped_outputs"]] == files
+        got.append([np.load(tmp_path / name / f) for f in files])
+    for a, b in zip(*got):
+        assert a.dtype == np.float32 and a.shape == (256, 256) and np.isfinite(a).all()
+        assert np.array_equal(a, b)
+    assert not np.array_equal(got[0][0], got[0][1])  # every pod has inputs of its own
+    assert sum(a.nbytes for a in got[0]) <= 64e6
+
+
+def test_dump_output_samples_a_large_output_within_its_budget(tmp_path):
+    import numpy as np
+    import torch
+    from vgpu.bench.pod import dump_output
+    t = torch.arange(10000, dtype=torch.bfloat16).reshape(100, 100)
+    info = dump_output([t[:50], t[50:]], str(tmp_path / "x.npy"), 1 << 20)
+    assert info["sampled"] is False and np.array_equal(np.load(tmp_path / "x.npy"), t.float().numpy())
+    info = dump_output(t, str(tmp_path / "y.npy"), 4000)
+    y = np.load(tmp_path / "y.npy")
+    assert info["sampled"] is True and y.dtype == np.float32 and y.nbytes <= 4000
+    dump_output(t, str(tmp_path / "z.npy"), 4000)
+    assert np.array_equal(y, np.load(tmp_path / "z.npy"))  # the same sample every time
+    assert set(y.tolist()) <= set(t.float().reshape(-1).tolist())
+
+
 def test_bench_two_ranks_gloo_cpu():
     port = _free_port()
     env = dict(os.environ)
     env.pop("HIP_VISIBLE_DEVICES", None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2",
-                        "--steps", "3", "--warmup", "1", "--pods", "2", "--cpu-smoke"],
+                        "--steps", "3", "--warmup", "1", "--pods", "2", "--cpu-smoke", "--full"],
                        cwd=REPO, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -57,7 +96,7 @@ def test_bench_eight_ranks_gloo_cpu_placement():
     env["HIP_VISIBLE_DEVICES"] = ",".join(str(i) for i in range(8))
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "8",
-                        "--steps", "2", "--warmup", "1", "--pods", "1", "--cpu-smoke"],
+                        "--steps", "2", "--warmup", "1", "--pods", "1", "--cpu-smoke", "--full"],
                        cwd=REPO, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

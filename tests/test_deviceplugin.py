@@ -204,14 +204,13 @@ class FakeKubelet:
 
 
 @pytest.fixture
-def cluster(tmp_path):
+def cluster(tmp_path, sock_dir):
     init_default_devices()
     config.SCHEDULER = config.SchedulerConfig()
     srv = FakeApiServer()
     url = srv.start()
     client = KubeClient(url)
-    sockdir = tmp_path / "dp"
-    sockdir.mkdir()
+    sockdir = sock_dir("dp")
     kubelet = FakeKubelet(str(sockdir / "kubelet.sock"))
     cfg = DevicePluginConfig(node_name="n1", device_split_count=4, socket_dir=str(sockdir),
                              host_lib_dir=str(tmp_path / "host"), config_file="", cu_share="mask")

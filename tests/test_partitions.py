@@ -103,14 +103,13 @@ def test_plan_strategies_on_a_mixed_node():
 
 
 @pytest.fixture
-def cpx_cluster(tmp_path):
+def cpx_cluster(tmp_path, sock_dir):
     def make(fx, strategy):
         init_default_devices()
         config.SCHEDULER = config.SchedulerConfig()
         srv = FakeApiServer()
         client = KubeClient(srv.start())
-        sockdir = tmp_path / f"dp-{strategy}"
-        sockdir.mkdir()
+        sockdir = sock_dir(f"dp-{strategy}")
         kubelet = FakeKubelet(str(sockdir / "kubelet.sock"))
         cfg = DevicePluginConfig(node_name="n1", device_split_count=4, socket_dir=str(sockdir),
                                  host_lib_dir=str(tmp_path / f"host-{strategy}"), config_file="", cu_share="mask",

@@ -92,7 +92,8 @@ def launch_pods(specs: list[PodSpec], device: str, *, steps: int, warmup: int, s
                 hw_queues: int | None = None, fused: bool = True,
                 conv: str = "native", cu_share: str = "temporal", memory_scaling: float = 1.0,
                 pool_concurrency: int = 0, seconds: float = 0.0, warmup_seconds: float = 0.0,
-                decide_timeout: float = 0.0) -> list[Pod]:
+                decide_timeout: float = 0.0, dump_outputs: str = "", dump_prefix: str = "",
+                dump_bytes: int = 0) -> list[Pod]:
     """Start one process per pod on physical device `device`.
 
     cu_share: how a fractional pod's compute share is enforced.
@@ -182,6 +183,10 @@ def launch_pods(specs: list[PodSpec], device: str, *, steps: int, warmup: int, s
             cmd += ["--warmup-seconds", str(warmup_seconds)]
         if decide_timeout > 0:
             cmd += ["--decide-timeout", str(decide_timeout), "--share-members", str(len(specs))]
+        if dump_outputs:
+            cmd += ["--dump-outputs", os.path.abspath(dump_outputs), "--dump-prefix", dump_prefix]
+            if dump_bytes > 0:
+                cmd += ["--dump-bytes", str(dump_bytes)]
         proc = subprocess.Popen(cmd, env=env, stdin=subprocess.PIPE, stdout=subprocess.PIPE,
                                 text=True, bufsize=1, cwd=str(REPO))
         pod = Pod(i, proc, cenv.get("VGPU_SHARED_REGION", ""), {k: v for k, v in cenv.items()})

@@ -10,6 +10,10 @@ Protocol (one JSON object per line on stdout, prefixed):
     <- "EXIT"
 Optional post-timing probe (--cap-probe): allocate 1 GiB blocks until the
 vGPU cap refuses, report how close to the cap that got (VRAM-cap accuracy).
+With --dump-outputs DIR the output of the last timed step (the logits of an
+inference workload, the loss of a training one) is written there as float32
+.npy before DONE; model and input are seeded per pod index, so two runs with
+the same arguments compute on identical inputs.
 
 Run standalone for debugging:  python -m vgpu.bench.pod --workload 1.1 --steps 5 --no-wait
 """
@@ -88,6 +92,7 @@ def build(args):
             loss = lossf(out, target)
             loss.backward()
             opt.step()
+            return loss
     else:
         model.eval()
         from vgpu.models.resnet import FusedResNetV2Inference, ResNetV2
@@ -119,7 +124,7 @@ def build(args):
             graph = torch.cuda.CUDAGraph()
             opt.zero_grad(set_to_none=True)
             with torch.cuda.graph(graph):
-                train_graph_body()
+                static_loss = train_graph_body()
         except Exception as e:  # an op without capture support (e.g. some RNN paths): eager
             sys.stderr.write(f"[pod {args.pod_index}] training hipGraph capture failed ({e}); eager\n")
             torch.cuda.synchronize()
@@ -127,6 +132,7 @@ def build(args):
 
         def replay_train():
             graph.replay()
+            return static_loss  # rewritten in place by every replay
         return w, replay_train
     if args.graph and not w.train:
         # Warm up on a side stream, then capture one step into a hipGraph:
@@ -144,7 +150,7 @@ def build(args):
         try:
             graph = torch.cuda.CUDAGraph()
             with torch.inference_mode(), torch.cuda.graph(graph):
-                model(x)
+                static_out = model(x)
         except Exception as e:  # e.g. an op without capture support: run eagerly
             sys.stderr.write(f"[pod {args.pod_index}] hipGraph capture failed ({e}); running eagerly\n")
             torch.cuda.synchronize()
@@ -152,6 +158,7 @@ def build(args):
 
         def replay():
             graph.replay()
+            return static_out  # rewritten in place by every replay
         return w, replay
     return w, step
 
@@ -171,11 +178,11 @@ def split_replay(model, x, split: int):
             with torch.cuda.stream(st):
                 model(xc)
     torch.cuda.synchronize()
-    graphs = []
+    graphs, outs = [], []
     for st, xc in zip(streams, chunks):
         g = torch.cuda.CUDAGraph()
         with torch.inference_mode(), torch.cuda.graph(g, stream=st):
-            model(xc)
+            outs.append(model(xc))
         graphs.append(g)
     torch.cuda.synchronize()
 
@@ -187,6 +194,7 @@ def split_replay(model, x, split: int):
                 g.replay()
         for st in streams:
             cur.wait_stream(st)
+        return outs  # one static output per micro-batch, in batch order
     return replay
 
 
@@ -238,6 +246,26 @@ def cap_probe() -> dict:
             "reserved_at_oom": reserved}
 
 
+def dump_output(out, path: str, max_bytes: int) -> dict:
+    """Write what the last timed step returned as one float32 .npy.  An output
+    larger than `max_bytes` is cut to a fixed, seeded sample of its elements
+    (the same indices in every run), flattened."""
+    import numpy as np
+    import torch
+    if isinstance(out, (list, tuple)):  # micro-batches, in batch order
+        out = torch.cat([o if o.dim() else o.reshape(1) for o in out])
+    t = out.detach().float().cpu()
+    keep = max(1, max_bytes // 4)
+    sampled = t.numel() > keep
+    if sampled:
+        g = torch.Generator().manual_seed(0)
+        idx = torch.randint(t.numel(), (keep,), generator=g).sort().values
+        t = t.reshape(-1)[idx]
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    np.save(path, t.numpy())
+    return {"file": os.path.basename(path), "shape": list(t.shape), "sampled": sampled}
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="1.1")
@@ -262,6 +290,10 @@ def main(argv=None) -> int:
                          "pods have decided between time sharing and CUs of their own, at most this long")
     ap.add_argument("--share-members", type=int, default=1,
                     help="pods that share this GPU and run at once (the decision --decide-timeout waits for)")
+    ap.add_argument("--dump-outputs", default="",
+                    help="after the timed steps, write the last step's output as <dir>/<prefix>pod<i>_<name>.npy")
+    ap.add_argument("--dump-prefix", default="")
+    ap.add_argument("--dump-bytes", type=int, default=32 << 20, help="size limit of the dumped array")
     args = ap.parse_args(argv)
 
     import torch
@@ -271,6 +303,7 @@ def main(argv=None) -> int:
         # orchestration rehearsal on a CPU-only host (tests): same protocol, tiny work
         from types import SimpleNamespace
         w = SimpleNamespace(batch=4)
+        torch.manual_seed(1234 + args.pod_index)
         a = torch.randn(256, 256)
 
         def step():
@@ -321,16 +354,17 @@ def main(argv=None) -> int:
     sync()
     t0 = time.monotonic()
     steps = args.steps
+    out = None  # what the last timed step handed its caller
     if args.seconds > 0:  # a fixed window: every pod of a share test runs the whole time
         steps = 0
         while time.monotonic() - t0 < args.seconds:
-            step()
+            out = step()
             steps += 1
             if steps % 8 == 0:
                 sync()  # keep the host within a few steps of the GPU
     else:
         for _ in range(steps):
-            step()
+            out = step()
     sync()
     t1 = time.monotonic()
     res = {"pod": args.pod_index, "t0": t0, "t1": t1, "steps": steps,
@@ -338,6 +372,9 @@ def main(argv=None) -> int:
            "throughput": steps * w.batch / max(t1 - t0, 1e-9)}
     if not cpu:
         res["share"] = share_state()  # the policy the timed window ran under
+    if args.dump_outputs and out is not None:
+        name = f"{args.dump_prefix}pod{args.pod_index}_{'loss' if getattr(w, 'train', False) else 'output'}.npy"
+        res["dumped"] = dump_output(out, os.path.join(args.dump_outputs, name), args.dump_bytes)
     if args.cap_probe and not cpu:
         res.update(cap_probe())
     emit("DONE", res)
