@@ -43,6 +43,11 @@ front for both modes (VGPU_CONTEXT_CHARGE), so both hold the same HBM.
     python -m vgpu.bench.vmem [--spill-gib 8] [--budget-gib 8] [--tokens 16] [--part-c]
     python -m vgpu.bench.vmem --part-d [--budget-gib 22] [--modes pager,zero_copy]
     python -m vgpu.bench.vmem --part-e [--budget-gib 11.5] [--context-charge-mib 0]
+    python -m vgpu.bench.vmem --part-r [--tokens 128] [--windows 6]    (resident decode_static / decode_native A/B)
+
+--native-decode: the graph-captured decode step of parts D and E is
+Llama.decode_native (native/kernels/decode.hip + the skinny GEMV) instead of
+stock PyTorch.  Off by default, so earlier records stay comparable.
 """
 from __future__ import annotations
 
@@ -288,7 +293,7 @@ def _stats_fn():
 class GraphDecoder:
     """A Llama-3-8B instance with its decode step captured as one hipGraph."""
 
-    def __init__(self, cfg, ctx: int, seed: int):
+    def __init__(self, cfg, ctx: int, seed: int, native: bool = False):
         import torch
         from vgpu.models.llama import Llama
         torch.manual_seed(seed)
@@ -304,15 +309,17 @@ class GraphDecoder:
         self.pos = torch.zeros(1, dtype=torch.long, device="cuda")
         self.ctx = ctx
         self.n = 0
+        # native: the step on the project's own kernels (Llama.decode_native) instead of stock PyTorch
+        step = self.m.decode_native if native else self.m.decode_static
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s), torch.inference_mode():
             for _ in range(2):
-                self.out = self.m.decode_static(self.tok, self.kv, self.pos)
+                self.out = step(self.tok, self.kv, self.pos)
         torch.cuda.current_stream().wait_stream(s)
         self.g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.g), torch.inference_mode():
-            self.out = self.m.decode_static(self.tok, self.kv, self.pos)
+            self.out = step(self.tok, self.kv, self.pos)
         torch.cuda.synchronize()
 
     def window(self, tokens: int) -> float:
@@ -326,7 +333,7 @@ class GraphDecoder:
         return round(tokens / (time.time() - t0), 2)
 
 
-def part_d_child(tokens: int, ctx: int, windows: int, idle_s: float) -> dict:
+def part_d_child(tokens: int, ctx: int, windows: int, idle_s: float, native: bool = False) -> dict:
     """Runs in the pod (libvgpu.so, oversubscribed, physical budget)."""
     import torch
     from vgpu.models.llama import LlamaConfig
@@ -334,13 +341,13 @@ def part_d_child(tokens: int, ctx: int, windows: int, idle_s: float) -> dict:
     cfg = LlamaConfig.llama3_8b()
     out = {}
     t0 = time.time()
-    a = GraphDecoder(cfg, ctx, 1)
+    a = GraphDecoder(cfg, ctx, 1, native)
     out["load_a_s"] = round(time.time() - t0, 2)
     out["a_first"] = [a.window(tokens) for _ in range(2)]
     out["after_a"] = stats()
     time.sleep(idle_s)  # A idles: its ranges go cold
     t0 = time.time()
-    b = GraphDecoder(cfg, ctx, 2)
+    b = GraphDecoder(cfg, ctx, 2, native)
     out["load_b_s"] = round(time.time() - t0, 2)
     out["after_load_b"] = stats()
     series = []
@@ -359,14 +366,48 @@ def part_d_child(tokens: int, ctx: int, windows: int, idle_s: float) -> dict:
     return out
 
 
-def part_e_child(tokens: int, ctx: int, windows: int) -> dict:
+def part_e_child(tokens: int, ctx: int, windows: int, native: bool = False) -> dict:
     from vgpu.models.llama import LlamaConfig
     stats = _stats_fn()
-    a = GraphDecoder(LlamaConfig.llama3_8b(), ctx, 1)
+    a = GraphDecoder(LlamaConfig.llama3_8b(), ctx, 1, native)
     out = {"after_load": stats()}
     t_rel = time.time()
     out["serving"] = [[round(time.time() - t_rel, 2), a.window(tokens)] for _ in range(windows)]
     out["final"] = stats()
+    return out
+
+
+def part_r(tokens: int, ctx: int, windows: int) -> dict:
+    """Resident graph decode, no shim: decode_static against decode_native on
+    one model's worth of weights each (same seed), windows alternating in one
+    process so that both see the same machine."""
+    import statistics
+
+    import torch
+    from vgpu.models.llama import LlamaConfig
+    cfg = LlamaConfig.llama3_8b()
+    dec = {"static": GraphDecoder(cfg, ctx, 1), "native": GraphDecoder(cfg, ctx, 1, native=True)}
+    for d in dec.values():  # the captured step at position 0 on an empty cache: the two paths' logits
+        for k, v in d.kv:
+            k.zero_()
+            v.zero_()
+        d.pos.fill_(0)
+        d.g.replay()
+    torch.cuda.synchronize()
+    a, b = dec["static"].out.float(), dec["native"].out.float()
+    out = {"ctx": ctx, "window_tokens": tokens,
+           "logits_pos0": {"max_abs_static": round(a.abs().max().item(), 4),
+                           "max_abs_diff": round((a - b).abs().max().item(), 4),
+                           "argmax_equal": bool(a.argmax() == b.argmax())}}
+    for d in dec.values():
+        d.window(tokens)  # warm
+        d.n = 0
+    series = {name: [] for name in dec}
+    for _ in range(windows):
+        for name, d in dec.items():
+            series[name].append(d.window(tokens))
+    for name, s in series.items():
+        out[name] = {"tok_s": s, "median": statistics.median(s), "min": min(s), "max": max(s)}
     return out
 
 
@@ -427,6 +468,10 @@ def main(argv=None) -> int:
     ap.add_argument("--idle-s", type=float, default=3.0)
     ap.add_argument("--context-charge-mib", type=int, default=0,
                     help="book this much runtime context at first use (both modes; see Part E)")
+    ap.add_argument("--part-r", action="store_true",
+                    help="resident graph decode, no shim: decode_static against decode_native, alternating windows")
+    ap.add_argument("--native-decode", action="store_true",
+                    help="parts D and E capture Llama.decode_native (the project's kernels) instead of decode_static")
     ap.add_argument("--skip-a", action="store_true")
     ap.add_argument("--skip-b", action="store_true")
     a = ap.parse_args(argv)
@@ -437,20 +482,25 @@ def main(argv=None) -> int:
         print("VMEM_C " + json.dumps(part_c_child(a.tokens, a.ctx, a.windows)), flush=True)
         return 0
     if a.child_d:
-        print("VMEM_D " + json.dumps(part_d_child(a.tokens, a.ctx, a.windows, a.idle_s)), flush=True)
+        print("VMEM_D " + json.dumps(part_d_child(a.tokens, a.ctx, a.windows, a.idle_s, a.native_decode)), flush=True)
         return 0
     if a.child_e:
-        print("VMEM_E " + json.dumps(part_e_child(a.tokens, a.ctx, a.windows)), flush=True)
+        print("VMEM_E " + json.dumps(part_e_child(a.tokens, a.ctx, a.windows, a.native_decode)), flush=True)
+        return 0
+    if a.part_r:
+        print("VMEM_R " + json.dumps(part_r(a.tokens, a.ctx, a.windows)), flush=True)
         return 0
     if a.part_d or a.part_e:
         part = "d" if a.part_d else "e"
         out = {"config": f"amd.com/gpumem=400000 (MiB), VGPU_OVERSUBSCRIBE=true, physical budget {a.budget_gib} GiB, "
                          + ("two Llama-3-8B bf16 (model switch)" if a.part_d else "one Llama-3-8B bf16")
-                         + ", decode step as one hipGraph replay, ctx " + str(a.ctx)}
+                         + ", decode step as one hipGraph replay, ctx " + str(a.ctx)
+                         + (", native decode kernels" if a.native_decode else "")}
         for mode in a.modes.split(","):
             out[mode] = run_pod_child(part, a.budget_gib, mode == "pager",
                                       ["--tokens", str(a.tokens), "--ctx", str(a.ctx), "--windows", str(a.windows),
-                                       "--idle-s", str(a.idle_s)], context_mib=a.context_charge_mib)
+                                       "--idle-s", str(a.idle_s)] + (["--native-decode"] if a.native_decode else []),
+                                      context_mib=a.context_charge_mib)
             print(f"VMEM_{part.upper()}_RUN " + json.dumps(out[mode]), flush=True)
         print(json.dumps(out), flush=True)
         return 0

@@ -160,6 +160,48 @@ class Llama(nn.Module):
             x = x + layer.w2(F.silu(g) * u)
         return self.head(self.norm(x))
 
+    @torch.no_grad()
+    def decode_native(self, tokens: torch.Tensor, kv_caches, pos: torch.Tensor) -> torch.Tensor:
+        """decode_static on the native kernels (vgpu.ops.decode): ten
+        dispatches per layer, K / V read in place for grouped-query attention,
+        `pos` read on the device (graph-capturable).  bf16 weights and
+        contiguous bf16 caches on the GPU, batch 1-4 or 8, head_dim 64 or 128;
+        anything else raises ValueError."""
+        from vgpu.ops import decode as D
+        D.check_llama_decode(self, tokens, kv_caches, pos)
+        cfg = self.cfg
+        B, dev = tokens.shape[0], tokens.device
+        H, KVH, hd = cfg.heads, cfg.kv_heads, cfg.dim // cfg.heads
+        ctx = kv_caches[0][0].shape[2] if kv_caches else 1
+        cos, sin = self.rope(dev)
+
+        def buf(*shape, dtype=torch.bfloat16):
+            return torch.empty(shape, dtype=dtype, device=dev)
+
+        x = self.embed(tokens).view(B, cfg.dim)  # the residual stream, updated in place
+        h, qkv, q = buf(B, cfg.dim), buf(B, (H + 2 * KVH) * hd), buf(B, H, hd)
+        att, ao, mlp = buf(B, H * hd), buf(B, cfg.dim), buf(B, cfg.dim)
+        gu, act = buf(B, 2 * cfg.ffn), buf(B, cfg.ffn)
+        ws = buf(D.attn_workspace_bytes(B, H, hd, ctx) // 4, dtype=torch.float32)
+        scale = hd ** -0.5
+        delta = None
+        for layer, (kc, vc) in zip(self.layers, kv_caches):
+            a = layer.attn
+            D.add_rmsnorm(x, delta, layer.norm1.weight, h, layer.norm1.eps)
+            D.gemv(h, a.wqkv.weight, qkv)
+            D.rope_kv_write(qkv, cos, sin, pos, q, kc, vc)
+            D.attn_decode(q, kc, vc, pos, att, ws, scale)
+            D.gemv(att, a.wo.weight, ao)
+            D.add_rmsnorm(x, ao, layer.norm2.weight, h, layer.norm2.eps)
+            D.gemv(h, layer.w13.weight, gu)
+            D.swiglu(gu, act)
+            D.gemv(act, layer.w2.weight, mlp)
+            delta = mlp
+        D.add_rmsnorm(x, delta, self.norm.weight, h, self.norm.eps)
+        logits = buf(B, cfg.vocab)
+        D.gemv(h, self.head.weight, logits)
+        return logits.view(B, 1, cfg.vocab)
+
     def new_kv_cache(self, batch: int, seq: int, dtype=torch.bfloat16, device=None):
         hd = self.cfg.dim // self.cfg.heads
         shape = (batch, self.cfg.kv_heads, seq, hd)
