@@ -96,6 +96,13 @@ struct ConvArgs {
   const uint8_t* pidx;
   uint16_t* gfull;
   int pk;
+  // "Post" epilogue (the POST kernel variants): the output feeds only the next
+  // projection block's shortcut and conv1, which both read it through that
+  // block's entry BN+ReLU, so p = relu(bf16(y)·qscale[c] + qshift[c]) is stored
+  // in place of y (fp32 [Cout] each) -- rounded exactly as conv_pro_kernel's
+  // prologue stages it, so those convs run prologue-free on identical operands.
+  const float* qscale;
+  const float* qshift;
 };
 
 // d act / d z as PyTorch defines it (threshold_backward / hardtanh_backward).
@@ -135,6 +142,17 @@ __device__ __forceinline__ void load8f(const float* p, float (&o)[8]) {
   const float4 b1 = *reinterpret_cast<const float4*>(p + 4);
   o[0] = b0.x; o[1] = b0.y; o[2] = b0.z; o[3] = b0.w;
   o[4] = b1.x; o[5] = b1.y; o[6] = b1.z; o[7] = b1.w;
+}
+
+// The post epilogue on 8 stored (bf16) values: relu(y·s + t) rounded to bf16, the
+// same expression as conv_pro_kernel's store_a and tail_epilogue's NEXT branch
+// (same rounding, same contraction).
+__device__ __forceinline__ u32x4 post_act8(const u32x4 y, const float (&sc)[8], const float (&sh)[8]) {
+  float q[8];
+  unpack8(y, q);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) q[j] = fmaxf(q[j] * sc[j] + sh[j], 0.0f);
+  return pack8(q);
 }
 
 __device__ __forceinline__ void load_bias8(const ConvArgs& a, int col, float (&bb)[8]) {
@@ -498,12 +516,14 @@ __device__ __forceinline__ void load_residual(const ConvArgs& a, int m0, int n0,
 // values), 2 backward (masked by the BN's activation derivative; ConvArgs::bnx).
 // NT threads = (NT / 128) x 2 waves; each row half is staged by the wave rows
 // that own it.
-template <int BM, int BN, bool RES, int ST = 0, int NT = kThreads>
+// POST: store relu(bf16(y)·qscale + qshift) in place of y (ConvArgs::qscale).
+template <int BM, int BN, bool RES, int ST = 0, int NT = kThreads, bool POST = false>
 __device__ __forceinline__ void epilogue_halves(const ConvArgs& a,
                                                 f32x4_t (&acc)[BM / (NT / 128) / 16][BN / 32],
                                                 int m0, int n0, char* smem,
                                                 const u32x4 (&res)[2][EpiShape<BM, BN, NT>::RROWS]) {
   static_assert(ST == 0 || NT == kThreads, "statistics: 256-thread tiles");
+  static_assert(!POST || ST == 0, "post epilogue: inference only");
   constexpr int WGM = NT / 128, WPH = WGM / 2;  // wave rows, wave rows per half
   constexpr int WTM = BM / WGM, WTN = BN / 2, TM = WTM / 16, TN = WTN / 16;
   constexpr int CS = BN + 4, HROWS = BM / 2;
@@ -516,6 +536,11 @@ __device__ __forceinline__ void epilogue_halves(const ConvArgs& a,
 #pragma unroll
   for (int j = 0; j < 8; ++j) bb[j] = 0.0f;
   if (a.bias) load_bias8(a, col, bb);
+  float qs[8], qt[8];
+  if constexpr (POST) {
+    load8f(a.qscale + col, qs);
+    load8f(a.qshift + col, qt);
+  }
   float* sC = reinterpret_cast<float*>(smem);
   // BatchNorm statistics (a.stats, uniform): per-thread sums over its rows, merged
   // per 64-row group through LDS past the staging area (the pipeline stages are free).
@@ -581,7 +606,8 @@ __device__ __forceinline__ void epilogue_halves(const ConvArgs& a,
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] *= bn_act_grad(a.bnact, fmaf(xf[j], bs[j], bt[j]));
       }
-      const u32x4 o = pack8(v);
+      u32x4 o = pack8(v);
+      if constexpr (POST) o = post_act8(o, qs, qt);
       if (m < a.M) *reinterpret_cast<u32x4*>(a.y + (int64_t)m * a.Cout + col) = o;
       if constexpr (st) {
         float q[8];
@@ -626,10 +652,13 @@ __device__ __forceinline__ void epilogue_halves(const ConvArgs& a,
 // DMA latency (a 3-stage ring measured slower on every ResNet-50 shape,
 // profiles/conv_stages_r1.md).  Prologue convs take conv_pro_kernel (an
 // in-register prologue on the DMA'd A fragments measured VALU-bound and slower).
-template <int KS, int BM, int BN, bool RES, int CSM = 0, int ST = 0, bool SPLIT = false>
+// POST: the post epilogue (ConvArgs::qscale), for the 1x1 + residual conv3 that
+// ends a stage.
+template <int KS, int BM, int BN, bool RES, int CSM = 0, int ST = 0, bool SPLIT = false, bool POST = false>
 __global__ void __launch_bounds__(kThreads, 2) conv_glds_kernel(const ConvArgs a) {
   static_assert(CSM == 0 || (64 % CSM == 0 && CSM % 8 == 0), "narrow-C variant");
   static_assert(!SPLIT || (!RES && ST == 0 && CSM == 0), "split-K: the reduce kernel does the epilogue");
+  static_assert(!POST || (KS == 1 && RES && CSM == 0 && ST == 0 && !SPLIT), "post epilogue: 1x1 + residual forward");
   constexpr int AR = BM / 32, BR = BN / 32;  // DMA instructions per thread per K step
   constexpr int WTM = BM / 2, WTN = BN / 2;
   constexpr int TM = WTM / 16, TN = WTN / 16;
@@ -767,13 +796,15 @@ __global__ void __launch_bounds__(kThreads, 2) conv_glds_kernel(const ConvArgs a
   if constexpr (RES) {
     if (!early_res) load_residual<BM, BN, ST == 2>(a, m0, n0, res);
   }
-  epilogue_halves<BM, BN, RES, ST>(a, acc, m0, n0, smem, res);
+  epilogue_halves<BM, BN, RES, ST, kThreads, POST>(a, acc, m0, n0, smem, res);
 }
 
 // Split-K epilogue: y = act(Σ_split ws[split] + bias (+ residual)) in bf16, the
 // splits summed in order (deterministic).  One thread = 8 channels of one row;
 // a block covers 256 / (Cout / 8) whole rows.  With gmask: y ·= [gmask > 0] and
 // the block's column sums of the stored values go to gpart[block].
+// POST: the post epilogue on the rounded sum (ConvArgs::qscale; no gmask / gfull).
+template <bool POST>
 __global__ void __launch_bounds__(kThreads) splitk_reduce_kernel(const ConvArgs a) {
   __shared__ float red[kThreads][9];
   const int cv = a.Cout >> 3;
@@ -840,7 +871,13 @@ __global__ void __launch_bounds__(kThreads) splitk_reduce_kernel(const ConvArgs 
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = mk[j] > 0.0f ? v[j] : 0.0f;
       }
-      const u32x4 o = pack8(v);
+      u32x4 o = pack8(v);
+      if constexpr (POST) {
+        float qs[8], qt[8];
+        load8f(a.qscale + col, qs);
+        load8f(a.qshift + col, qt);
+        o = post_act8(o, qs, qt);
+      }
       *reinterpret_cast<u32x4*>(a.y + off) = o;
       unpack8(o, v);  // the partial sums add the stored (rounded) values
     }
@@ -1424,13 +1461,21 @@ int g_forced_big = -1;  // vgpu_conv_set_big: -1 = env VGPU_CONV_BIG / heuristic
 
 int g_forced_bm = 0;  // vgpu_conv_set_tile_m (A/B benchmarking); 0 = heuristic
 
-template <int KS, int BM, int BN, bool RES, int CSM = 0, int ST = 0>
+template <int KS, int BM, int BN, bool RES, int CSM = 0, int ST = 0, bool POST = false>
 hipError_t launch_glds(ConvArgs a, hipStream_t s) {
   a.nM = (a.M + BM - 1) / BM;
   a.nN = a.Cout / BN;
   a.nwg = a.nM * a.nN;
-  hipLaunchKernelGGL((conv_glds_kernel<KS, BM, BN, RES, CSM, ST>), dim3(a.nwg), dim3(kThreads), 0, s, a);
+  hipLaunchKernelGGL((conv_glds_kernel<KS, BM, BN, RES, CSM, ST, false, POST>), dim3(a.nwg), dim3(kThreads), 0, s,
+                     a);
   return hipGetLastError();
+}
+
+// 1x1 + residual with the post epilogue (ConvArgs::qscale)
+template <int BM>
+hipError_t dispatch_glds_post(const ConvArgs& a, hipStream_t s) {
+  if (a.Cout % 128 == 0) return launch_glds<1, BM, 128, true, 0, 0, true>(a, s);
+  return launch_glds<1, BM, 64, true, 0, 0, true>(a, s);
 }
 
 template <int KS, int BM>
@@ -1694,7 +1739,9 @@ hipError_t dispatch_pro(const ConvArgs& a, bool res, hipStream_t s) {
 // rounded to bf16 exactly as conv_pro's prologue stages it) for this thread's
 // rows, into registers; s/t are read from LDS (sPs/sPt), never from global
 // memory, for the same reason.
-template <int BM, int BN, bool NEXT, int NT = kThreads, typename Mid>
+// POST: that p is stored in place of y (the post epilogue: the next block is a
+// projection block, nobody reads y itself); pv is not written.
+template <int BM, int BN, bool NEXT, int NT = kThreads, bool POST = false, typename Mid>
 __device__ __forceinline__ void tail_epilogue(const ConvArgs& a, f32x4_t (&acc)[BM / (NT / 128) / 16][BN / 32],
                                               int m0, int n0, char* smem,
                                               const u32x4 (&res)[2][EpiShape<BM, BN, NT>::RROWS],
@@ -1709,8 +1756,9 @@ __device__ __forceinline__ void tail_epilogue(const ConvArgs& a, f32x4_t (&acc)[
   const int chunk = t % E::CPR, rfirst = t / E::CPR;
   const int col = n0 + chunk * 8;
   const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, a.y_bytes, 0x00020000);
+  static_assert(!(NEXT && POST), "the next block's conv1 is fused only behind an identity shortcut");
   float sc[8], sh[8];
-  if constexpr (NEXT) {
+  if constexpr (NEXT || POST) {
     const float4 s0 = *reinterpret_cast<const float4*>(sPs + col);
     const float4 s1 = *reinterpret_cast<const float4*>(sPs + col + 4);
     const float4 h0 = *reinterpret_cast<const float4*>(sPt + col);
@@ -1757,7 +1805,8 @@ __device__ __forceinline__ void tail_epilogue(const ConvArgs& a, f32x4_t (&acc)[
 #pragma unroll
     for (int i = 0; i < E::RROWS; ++i) {
       const int r = rfirst + E::RSTEP * i, m = m0 + h * HROWS + r;
-      const u32x4 yv = pack8(v[i]);
+      u32x4 yv = pack8(v[i]);
+      if constexpr (POST) yv = post_act8(yv, sc, sh);
       __builtin_amdgcn_raw_buffer_store_b128(yv, yr, m < a.M ? (uint32_t)(((int64_t)m * a.Cout + col) * 2) : kOOB,
                                              0, 0);
       if constexpr (NEXT) {
@@ -1803,7 +1852,9 @@ __device__ __forceinline__ void tail_epilogue(const ConvArgs& a, f32x4_t (&acc)[
 // L2 traffic per row (profiles/r5/kernels/pmc_l2_r5.md) -- and a 3-stage vs a
 // 2-stage conv2 ring: the ring won 0.5 %, the wide tile lost 0.5 % (one
 // workgroup per CU); the tails are latency-, not L2-bandwidth-bound.
-template <int BM, int W, bool NEXT = false, int NS1 = 3, int NT = kThreads>
+// POST: the block ends a stage -- its output is stored through the post
+// epilogue (ConvArgs::qscale of b, staged in LDS like NEXT's parameters).
+template <int BM, int W, bool NEXT = false, int NS1 = 3, int NT = kThreads, bool POST = false>
 __global__ void __launch_bounds__(NT, 512 / NT) conv23_kernel(const ConvArgs a, const ConvArgs b,
                                                               const ConvArgs c) {
   constexpr int KCH = W / 64;                // conv3 K chunks (64 channels each)
@@ -1825,7 +1876,7 @@ __global__ void __launch_bounds__(NT, 512 / NT) conv23_kernel(const ConvArgs a, 
   constexpr int P = P1 > P2 ? P1 : P2;
   // conv2 bias [W] and (NEXT) conv1's prologue scale/shift [4W] each live in
   // LDS: a global load in phase 2 would make hipcc drain the in-flight DMA.
-  constexpr int PAR = (W + (NEXT ? 8 * W : 0)) * 4;
+  constexpr int PAR = (W + (NEXT || POST ? 8 * W : 0)) * 4;
   static_assert(P + PAR <= 160 * 1024, "conv23: LDS");
   static_assert(NT == 512 || 2 * (P + PAR) <= 160 * 1024, "conv23: two workgroups per CU");
   __shared__ __attribute__((aligned(16))) char smem[P + PAR];
@@ -1861,10 +1912,12 @@ __global__ void __launch_bounds__(NT, 512 / NT) conv23_kernel(const ConvArgs a, 
   const uint32_t boff = (uint32_t)((lrow * a.K + lchunk * 8) * 2);
   for (int i = t * 4; i < W; i += NT * 4)
     *reinterpret_cast<float4*>(sPar + i) = *reinterpret_cast<const float4*>(a.bias + i);
-  if constexpr (NEXT) {
+  if constexpr (NEXT || POST) {
+    const float* ps = NEXT ? c.pscale : b.qscale;
+    const float* pt = NEXT ? c.pshift : b.qshift;
     for (int i = t * 4; i < 4 * W; i += NT * 4) {
-      *reinterpret_cast<float4*>(sPar + W + i) = *reinterpret_cast<const float4*>(c.pscale + i);
-      *reinterpret_cast<float4*>(sPar + 5 * W + i) = *reinterpret_cast<const float4*>(c.pshift + i);
+      *reinterpret_cast<float4*>(sPar + W + i) = *reinterpret_cast<const float4*>(ps + i);
+      *reinterpret_cast<float4*>(sPar + 5 * W + i) = *reinterpret_cast<const float4*>(pt + i);
     }
   }
   __syncthreads();
@@ -2016,7 +2069,8 @@ __global__ void __launch_bounds__(NT, 512 / NT) conv23_kernel(const ConvArgs a, 
     u32x4 pv[2][E2::RROWS];
     if constexpr (!NEXT) {
       const bool more = ch + 1 < nchunks;
-      tail_epilogue<BM, BN2, false, NT>(b, acc2, m0, c0, sE, res, sPar, sPar, pv, [&] {
+      tail_epilogue<BM, BN2, false, NT, POST>(b, acc2, m0, c0, sE, res, sPar + (POST ? W : 0),
+                                              sPar + (POST ? 5 * W : 0), pv, [&] {
         if (more) issue_w3(ch + 1);
       });
       if (more) load_residual<BM, BN2, false, NT>(b, m0, c0 + BN2, res);
@@ -2287,14 +2341,19 @@ __global__ void __launch_bounds__(kThreads) s2d_stem_kernel(const uint16_t* __re
 // consecutive channels of one pixel.  K order (kh, kw, c) and the MFMA
 // sequence match the unfused stem conv, so the result is bit-identical to
 // conv + maxpool (tests/test_gpu_conv.py).
+// POST: the pooled row goes out through the post epilogue, relu(y·qs[c] + qt[c])
+// (the entry BN+ReLU of the first block, whose two convs are its only readers).
 constexpr int kSPThreads = 512;
 constexpr int kSPMaxOW = 176;   // 11 pixel subtiles of 16
 constexpr int kSPMaxWS = 180;
 
+template <bool POST>
 __global__ void __launch_bounds__(kSPThreads, 1) stem_pool_kernel(const uint16_t* __restrict__ X,
                                                                   const uint16_t* __restrict__ w,
                                                                   uint16_t* __restrict__ y, int HS, int WS,
-                                                                  int OH, int OW, int PH, int PW, int tasks) {
+                                                                  int OH, int OW, int PH, int PW, int tasks,
+                                                                  const float* __restrict__ qs,
+                                                                  const float* __restrict__ qt) {
   constexpr int SW_BYTES = 4 * 64 * 128;         // [kh][cout][128 B] swizzled
   constexpr int SR_BYTES = 3 * kSPMaxOW * 128;   // three bf16 stem rows [row][pixel][64 ch] swizzled
   constexpr int SX_BYTES = 6 * kSPMaxWS * 32 + 512;  // 6 input rows [px][16 ch] + over-read pad
@@ -2333,6 +2392,12 @@ __global__ void __launch_bounds__(kSPThreads, 1) stem_pool_kernel(const uint16_t
       if (k < nchunk) *reinterpret_cast<u32x4*>(sX + k * 16) = xr[u];
     }
   };
+  // post parameters of this thread's 8 pooled channels (q = t & 7 in the window loop)
+  float psc[8], psh[8];
+  if constexpr (POST) {
+    load8f(qs + (t & 7) * 8, psc);
+    load8f(qt + (t & 7) * 8, psh);
+  }
   u32x4 xr[XR];
   int task = blockIdx.x;
   if (task < tasks) {
@@ -2408,7 +2473,9 @@ __global__ void __launch_bounds__(kSPThreads, 1) stem_pool_kernel(const uint16_t
           for (int u = 0; u < 8; ++u) pm[u] = fmaxf(pm[u], e[u]);
         }
       }
-      *reinterpret_cast<u32x4*>(y + ((int64_t)(n * PH + pi) * PW + j) * 64 + q * 8) = pack8(pm);
+      u32x4 o = pack8(pm);  // exact: pm are bf16 values
+      if constexpr (POST) o = post_act8(o, psc, psh);
+      *reinterpret_cast<u32x4*>(y + ((int64_t)(n * PH + pi) * PW + j) * 64 + q * 8) = o;
     }
     if (next < tasks) {
       __syncthreads();  // every wave done with the slab and the row buffers
@@ -2440,12 +2507,16 @@ VGPU_API unsigned long long vgpu_conv_halo_launches() { return g_halo_launches; 
 // Fused conv2 (3x3, pad 1, stride s, C = W → W, bias + ReLU) + conv3 (1x1,
 // W → 4W) + residual; with w1n, also the next block's conv1 (1x1, 4W → W,
 // prologue relu(y*ps + pt), bias b1n + ReLU) into h1n.  W ∈ {64, 128}.
+// qs/qt (both or neither, not with w1n): the post epilogue, y holds
+// relu(y·qs + qt) for the projection block that follows.
 static int conv23_impl(const void* x, const void* w2, const float* b2, const void* w3, const void* res,
                        void* y, const void* w1n, const float* b1n, const float* psn, const float* ptn,
-                       void* h1n, int N, int H, int W, int C, int stride, hipStream_t s) {
+                       void* h1n, int N, int H, int W, int C, int stride, hipStream_t s,
+                       const float* qs = nullptr, const float* qt = nullptr) {
   if ((C != 64 && C != 128) || stride < 1 || N < 1 || !b2 || !res) return -1;
-  const bool next = w1n != nullptr;
+  const bool next = w1n != nullptr, post = qs != nullptr;
   if (next && (!b1n || !psn || !ptn || !h1n)) return -1;
+  if ((qs == nullptr) != (qt == nullptr) || (post && next)) return -1;
   ConvArgs a{};
   a.x = static_cast<const uint16_t*>(x);
   a.w = static_cast<const uint16_t*>(w2);
@@ -2464,6 +2535,8 @@ static int conv23_impl(const void* x, const void* w2, const float* b2, const voi
   b.res = static_cast<const uint16_t*>(res);
   b.Cout = 4 * C;
   b.K = C;
+  b.qscale = qs;
+  b.qshift = qt;
   ConvArgs cn{};
   if (next) {
     cn.w = static_cast<const uint16_t*>(w1n);
@@ -2501,11 +2574,17 @@ static int conv23_impl(const void* x, const void* w2, const float* b2, const voi
     if (C == 64) {
       if (next)
         hipLaunchKernelGGL((conv23_kernel<128, 64, true>), dim3(c.nwg), dim3(kThreads), 0, s, c, d, e);
+      else if (post)
+        hipLaunchKernelGGL((conv23_kernel<128, 64, false, 3, kThreads, true>), dim3(c.nwg), dim3(kThreads), 0, s, c,
+                           d, e);
       else
         hipLaunchKernelGGL((conv23_kernel<128, 64>), dim3(c.nwg), dim3(kThreads), 0, s, c, d, e);
     } else {
       if (next)
         hipLaunchKernelGGL((conv23_kernel<64, 128, true>), dim3(c.nwg), dim3(kThreads), 0, s, c, d, e);
+      else if (post)
+        hipLaunchKernelGGL((conv23_kernel<64, 128, false, 3, kThreads, true>), dim3(c.nwg), dim3(kThreads), 0, s, c,
+                           d, e);
       else
         hipLaunchKernelGGL((conv23_kernel<64, 128>), dim3(c.nwg), dim3(kThreads), 0, s, c, d, e);
     }
@@ -2519,6 +2598,17 @@ VGPU_API int vgpu_conv23_nhwc(const void* x, const void* w2, const float* b2, co
                               const void* res, void* y, int N, int H, int W, int C, int stride,
                               hipStream_t s) {
   return conv23_impl(x, w2, b2, w3, res, y, nullptr, nullptr, nullptr, nullptr, nullptr, N, H, W, C, stride, s);
+}
+
+// vgpu_conv23_nhwc with the post epilogue: y = relu(bf16(conv23)·qs[c] + qt[c]),
+// qs/qt fp32 [4C] -- the entry BN+ReLU of the projection block that follows,
+// whose shortcut and conv1 then run without a prologue on identical operands.
+VGPU_API int vgpu_conv23_post_nhwc(const void* x, const void* w2, const float* b2, const void* w3,
+                                   const void* res, void* y, const float* qs, const float* qt, int N, int H,
+                                   int W, int C, int stride, hipStream_t s) {
+  if (!qs || !qt) return -1;
+  return conv23_impl(x, w2, b2, w3, res, y, nullptr, nullptr, nullptr, nullptr, nullptr, N, H, W, C, stride, s,
+                     qs, qt);
 }
 
 // conv23 + the next (identity-shortcut) block's conv1 in one kernel: y is the
@@ -2537,7 +2627,8 @@ int conv2d_impl(const void* x, const void* w, void* y, const void* res, const fl
                 const float* pshift, int N, int H, int W, int C, int Cout, int KS, int stride, int pad, int act,
                 float* stats, const void* bnx, const float* bncoef, int bnact, int res_stride, hipStream_t s,
                 float* ws = nullptr, int64_t ws_bytes = 0, const void* gmask = nullptr, float* gpart = nullptr,
-                const void* pidx = nullptr, void* gfull = nullptr, int pk = 0);
+                const void* pidx = nullptr, void* gfull = nullptr, int pk = 0, const float* qscale = nullptr,
+                const float* qshift = nullptr);
 
 int g_forced_split = -1;  // vgpu_conv_set_splitk: -1 heuristic, 0 off, n > 1 that many splits when eligible
 
@@ -2595,6 +2686,19 @@ VGPU_API int vgpu_conv2d_nhwc_ws(const void* x, const void* w, void* y, const vo
                                  int KS, int stride, int pad, int act, void* ws, int64_t ws_bytes, hipStream_t s) {
   return conv2d_impl(x, w, y, res, static_cast<const float*>(bias), pscale, pshift, N, H, W, C, Cout, KS, stride,
                      pad, act, nullptr, nullptr, nullptr, 0, 1, s, static_cast<float*>(ws), ws_bytes);
+}
+
+// vgpu_conv2d_nhwc_ws for a 1x1 conv + residual with the post epilogue:
+// y = relu(bf16(conv(x, w) + res)·qs[c] + qt[c]), qs/qt fp32 [Cout] -- the entry
+// BN+ReLU of the projection block that follows.  -1 (before any launch) for
+// anything but the LDS-DMA 1x1 + residual kernels and their split-K form.
+VGPU_API int vgpu_conv2d_post_nhwc_ws(const void* x, const void* w, void* y, const void* res, const float* qs,
+                                      const float* qt, int N, int H, int W, int C, int Cout, int stride, void* ws,
+                                      int64_t ws_bytes, hipStream_t s) {
+  if (!qs || !qt || !res) return -1;
+  return conv2d_impl(x, w, y, res, nullptr, nullptr, nullptr, N, H, W, C, Cout, 1, stride, 0, 0, nullptr, nullptr,
+                     nullptr, 0, 1, s, static_cast<float*>(ws), ws_bytes, nullptr, nullptr, nullptr, nullptr, 0, qs,
+                     qt);
 }
 
 VGPU_API void vgpu_conv_set_splitk(int mode) { g_forced_split = mode; }
@@ -2664,7 +2768,7 @@ int conv2d_impl(const void* x, const void* w, void* y, const void* res, const fl
                 const float* pshift, int N, int H, int W, int C, int Cout, int KS, int stride, int pad, int act,
                 float* stats, const void* bnx, const float* bncoef, int bnact, int res_stride, hipStream_t s,
                 float* ws, int64_t ws_bytes, const void* gmask, float* gpart, const void* pidx, void* gfull,
-                int pk) {
+                int pk, const float* qscale, const float* qshift) {
   const int bias_bf16 = (act >> 8) & 1;
   act &= 0xff;
   if (act > 2) return -1;
@@ -2706,11 +2810,18 @@ int conv2d_impl(const void* x, const void* w, void* y, const void* res, const fl
   }
   const bool pro = pscale != nullptr, has_res = res != nullptr;
   if (stats && (narrow || pro)) return -1;
+  // Post epilogue: the 1x1 + residual LDS-DMA kernels (and their split-K reduce) only.
+  const bool post = qscale != nullptr;
+  if ((qscale == nullptr) != (qshift == nullptr)) return -1;
+  if (post && (KS != 1 || pro || !has_res || stats || gmask || act != 0 || bias)) return -1;
+  a.qscale = qscale;
+  a.qshift = qshift;
   // Buffer offsets are 32-bit: run the batch in slices whose activations stay < 2 GiB.
   const int64_t xi = (int64_t)H * W * C * 2, yi = (int64_t)a.OH * a.OW * Cout * 2;
   const int64_t lim = ((int64_t)1 << 31) - 1;
   const int64_t per = lim / (xi > yi ? xi : yi);
   if (per < 1 || (stats && per < N)) return -1;  // statistics: one slice (group rows are global)
+  if (post && per < N) return -1;  // one slice, so -1 comes before any launch
   const int bn = (Cout % 128 == 0) ? 128 : 64;
   for (int n0 = 0; n0 < N; n0 += (int)per) {
     const int nb = (int)((N - n0) < per ? (N - n0) : per);
@@ -2730,8 +2841,13 @@ int conv2d_impl(const void* x, const void* w, void* y, const void* res, const fl
     bool small = tiles128 < (int64_t)conv_cus() * 3 / 2;
     // Non-prologue 1x1 convs (conv3 + residual) are DMA/HBM-bound: 64-row tiles
     // (48 KB LDS → 3 blocks per CU) beat 128-row tiles on every ResNet-50 shape
-    // (profiles/conv_tiles_r1.md).
-    if (!pro && KS == 1) small = !conv_1x1_big();
+    // (profiles/conv_tiles_r1.md).  Without a residual, from K = 256 and 128
+    // outputs up -- a projection block's shortcut and conv1 on a pre-activated
+    // input -- 128-row tiles measured 2-7 % ahead on all six such flagship
+    // shapes (profiles/r7/preact), so those keep the grid-fill rule above;
+    // K = 64 (block 0) stays on 64-row tiles (tie / 6 % behind).
+    const bool rows128_ok = !has_res && !stats && C >= 256 && Cout >= 128;
+    if (!pro && KS == 1 && !rows128_ok) small = !conv_1x1_big();
     if (g_forced_bm == 64) small = true;
     if (g_forced_bm == 128) small = false;
     hipError_t e;
@@ -2761,8 +2877,8 @@ int conv2d_impl(const void* x, const void* w, void* y, const void* res, const fl
       }
       if ((e = hipGetLastError()) != hipSuccess) return (int)e;
       const int64_t threads = (int64_t)c.M * (Cout / 8);
-      hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((threads + kThreads - 1) / kThreads)), dim3(kThreads),
-                         0, s, c);
+      hipLaunchKernelGGL(post ? splitk_reduce_kernel<true> : splitk_reduce_kernel<false>,
+                         dim3((unsigned)((threads + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, c);
       if ((e = hipGetLastError()) != hipSuccess) return (int)e;
       continue;
     }
@@ -2785,7 +2901,10 @@ int conv2d_impl(const void* x, const void* w, void* y, const void* res, const fl
     // 3x3 / stride 1 without prologue or residual: the halo-tile kernel.
     const bool halo = (g_forced_halo < 0 ? halo_enabled() : g_forced_halo > 0) && !narrow && !pro && !has_res &&
                       KS == 3 && stride == 1 && pad == 1;
-    if (halo && (e = dispatch_halo(c, s)) != hipErrorNotSupported) {
+    if (post) {
+      if (big) return -1;  // the 256x256 tile has no post epilogue (first launch of the only slice)
+      e = small ? dispatch_glds_post<64>(c, s) : dispatch_glds_post<128>(c, s);
+    } else if (halo && (e = dispatch_halo(c, s)) != hipErrorNotSupported) {
       // launched (or a launch error)
     } else if (big)
       e = has_res ? launch_big<true>(c, s) : launch_big<false>(c, s);
@@ -2814,7 +2933,8 @@ int conv2d_impl(const void* x, const void* w, void* y, const void* res, const fl
 // NHWC bf16 max pool (k×k window, stride, symmetric zero-excluded padding), 16 B per lane.
 // Fused stem: X [N][HS][WS][16] (space-to-depth input), w [64][4][4][16] →
 // y [N][PH][PW][64] = maxpool3x3/s2/p1(conv4x4/s1(X, w)), bf16 NHWC.
-VGPU_API int vgpu_stem_pool_nhwc(const void* X, const void* w, void* y, int N, int HS, int WS, hipStream_t s) {
+static int stem_pool_impl(const void* X, const void* w, void* y, const float* qs, const float* qt, int N, int HS,
+                          int WS, hipStream_t s) {
   const int OH = HS - 3, OW = WS - 3;
   if (N < 1 || OH < 1 || OW < 1 || OW > kSPMaxOW || WS > kSPMaxWS) return -1;
   if ((int64_t)N * HS * WS * 16 >= ((int64_t)1 << 31)) return -1;
@@ -2829,9 +2949,22 @@ VGPU_API int vgpu_stem_pool_nhwc(const void* X, const void* w, void* y, int N, i
       hipDeviceGetAttribute(&grid, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || grid < 1)
     grid = 256;
   if (grid > tasks) grid = tasks;
-  hipLaunchKernelGGL(stem_pool_kernel, dim3(grid), dim3(kSPThreads), 0, s, static_cast<const uint16_t*>(X),
-                     static_cast<const uint16_t*>(w), static_cast<uint16_t*>(y), HS, WS, OH, OW, PH, PW, tasks);
+  hipLaunchKernelGGL(qs ? stem_pool_kernel<true> : stem_pool_kernel<false>, dim3(grid), dim3(kSPThreads), 0, s,
+                     static_cast<const uint16_t*>(X), static_cast<const uint16_t*>(w), static_cast<uint16_t*>(y), HS,
+                     WS, OH, OW, PH, PW, tasks, qs, qt);
   return (int)hipGetLastError();
+}
+
+VGPU_API int vgpu_stem_pool_nhwc(const void* X, const void* w, void* y, int N, int HS, int WS, hipStream_t s) {
+  return stem_pool_impl(X, w, y, nullptr, nullptr, N, HS, WS, s);
+}
+
+// vgpu_stem_pool_nhwc with the post epilogue: y = relu(pool·qs[c] + qt[c]), qs/qt
+// fp32 [64] (the first block's entry BN+ReLU).  Same shapes, same -1.
+VGPU_API int vgpu_stem_pool_post_nhwc(const void* X, const void* w, void* y, const float* qs, const float* qt,
+                                      int N, int HS, int WS, hipStream_t s) {
+  if (!qs || !qt) return -1;
+  return stem_pool_impl(X, w, y, qs, qt, N, HS, WS, s);
 }
 
 VGPU_API int vgpu_maxpool_nhwc(const void* x, void* y, int N, int H, int W, int C, int k, int stride,

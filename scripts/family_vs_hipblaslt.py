@@ -10,6 +10,11 @@ build, a ceiling in its favour.  Both are timed as 20 launches replayed from
 one hipGraph, in-process.  conv23 (conv2 + conv3 + residual fused) is compared
 with the two hipBLASLt GEMMs it replaces.
 
+The eight convs of the projection blocks (shortcut and conv1 of b0, b3, b7,
+b13) are listed in both forms on one tree: the BN+ReLU prologue conv on the raw
+tensor (FusedResNetV2Inference(preact=False)) and the plain conv on the tensor
+its producer stored pre-activated (the default runner).
+
     python scripts/family_vs_hipblaslt.py > profiles/r6/kernels/family_vs_hipblaslt.json
 """
 from __future__ import annotations
@@ -64,10 +69,25 @@ def main() -> int:
         ("conv 3x3", "s3 conv2 3x3 256 @22", 256, 22, 256, 3, 1, False, False),
         ("conv 3x3", "s4 conv2 3x3 512 @11", 512, 11, 512, 3, 1, False, False),
     ]
+    # projection blocks: name, C, H, Cout, stride -- prologue form, then pre-activated form
+    for name, c, h, cout, stride in (("b0 shortcut 64->256 @87", 64, 87, 256, 1),
+                                     ("b0 conv1 64->64 @87", 64, 87, 64, 1),
+                                     ("b3 shortcut 256->512 s2 @87", 256, 87, 512, 2),
+                                     ("b3 conv1 256->128 @87", 256, 87, 128, 1),
+                                     ("b7 shortcut 512->1024 s2 @44", 512, 44, 1024, 2),
+                                     ("b7 conv1 512->256 @44", 512, 44, 256, 1),
+                                     ("b13 shortcut 1024->2048 s2 @22", 1024, 22, 2048, 2),
+                                     ("b13 conv1 1024->512 @22", 1024, 22, 512, 1)):
+        layers.append(("boundary, prologue", name + " raw + prologue", c, h, cout, 1, stride, True, False))
+        layers.append(("boundary, pre-activated", name + " pre-activated", c, h, cout, 1, stride, False, False, True))
     out = []
     g = torch.Generator(device="cpu").manual_seed(0)
-    for fam, name, c, h, cout, ks, stride, pro, res in layers:
+    for fam, name, c, h, cout, ks, stride, pro, res, *pre in layers:
         x = torch.randn(b, c, h, h, generator=g).to(dev, torch.bfloat16).contiguous(memory_format=CL)
+        if pre:  # the data the plain conv sees in the model: a BN+ReLU output
+            x = (x.float() * (torch.rand(c, device=dev) + 0.5).view(1, -1, 1, 1)
+                 + (torch.randn(c, device=dev) * 0.1).view(1, -1, 1, 1)).clamp_min(0).to(torch.bfloat16)
+            x = x.contiguous(memory_format=CL)
         w = (torch.randn(cout, c, ks, ks, generator=g) * 0.05).to(dev, torch.bfloat16).contiguous(memory_format=CL)
         pad = ks // 2
         oh = (h + 2 * pad - ks) // stride + 1

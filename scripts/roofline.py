@@ -8,7 +8,9 @@ and the time it cannot beat on one MI355X (8 TB/s HBM3E, 2.5 PFLOP/s dense bf16)
 
 CPU only: the plan is derived from the model's layer shapes, mirroring the
 dispatch decisions of `_forward_native` (conv23/conv231 fusion for C in
-{64, 128}; separate conv2/conv3 otherwise).  `--measured-ms` is the bench's
+{64, 128}; separate conv2/conv3 otherwise; the input of a projection block
+stored pre-activated by its producer, so that block's shortcut and conv1 carry
+no prologue -- same bytes and FLOPs either way).  `--measured-ms` is the bench's
 ms_per_step (all pods) to compare against.
 """
 from __future__ import annotations
@@ -57,10 +59,12 @@ def plan(batch: int, size: int, layers=(3, 4, 6, 3)):
         ho = conv_out(h, 3, stride, 1)
         m_out = batch * ho * ho
         if proj:
-            out.append((f"b{bi} shortcut 1x1 (BN+ReLU prologue)", 2 * m_out * ci * co,
+            out.append((f"b{bi} shortcut 1x1 (pre-activated input)", 2 * m_out * ci * co,
                         E * (m_in * ci + m_out * co + ci * co)))
         if not h_next_ready:
-            out.append((f"b{bi} conv1 1x1 (BN+ReLU prologue)", 2 * m_in * ci * wd, E * (m_in * ci + m_in * wd + ci * wd)))
+            # only projection blocks reach here (an identity block's conv1 is fused into the previous tail)
+            kind = "pre-activated input" if proj else "BN+ReLU prologue"
+            out.append((f"b{bi} conv1 1x1 ({kind})", 2 * m_in * ci * wd, E * (m_in * ci + m_in * wd + ci * wd)))
         h_next_ready = False
         nxt = blocks[bi + 1] if bi + 1 < len(blocks) else None
         f2 = 2 * m_out * 9 * wd * wd

@@ -11,6 +11,8 @@ add and cannot be folded).
 """
 from __future__ import annotations
 
+import functools
+
 import torch
 from torch import nn
 import torch.nn.functional as F
@@ -142,12 +144,21 @@ class FusedResNetV2Inference(nn.Module):
 
     conv="native" (default): every convolution after the stem is the MFMA
     implicit-GEMM kernel of native/kernels/conv_gemm.hip with its neighbours
-    fused in — the block-entry BN+ReLU as the prologue of conv1 and of the
-    projection shortcut, folded-BN bias + ReLU as the epilogue of conv1/conv2,
-    the residual add as the epilogue of conv3 — so a bottleneck is 3 (or 4)
-    kernels and the pre-activation tensor is never materialised.  The stem
-    7x7/s2 stem runs as space-to-depth + a 4x4 narrow-C MFMA conv; its
-    max-pool and the final BN+ReLU+global-mean are hand-written kernels too.
+    fused in — the block-entry BN+ReLU as the prologue of an identity block's
+    conv1, folded-BN bias + ReLU as the epilogue of conv1/conv2, the residual
+    add as the epilogue of conv3 — so a bottleneck is 3 (or 4) kernels.  The
+    7x7/s2 stem runs as space-to-depth + a 4x4 narrow-C MFMA conv with its
+    max-pool fused; the final BN+ReLU+global-mean is a hand-written kernel too.
+
+    preact=True (default): the tensor that enters a projection block (the first
+    block of a stage) is read only by that block's shortcut and conv1, both
+    through its entry BN+ReLU, so its producer -- the stem, or the previous
+    stage's last conv3 -- stores it pre-activated ("post" epilogue, rounded as
+    the prologue would round it) and those two convs run on the prologue-free
+    LDS-DMA kernels; logits are bit-identical to preact=False, which keeps the
+    prologue on those convs.  Where a producer has no post form for a shape,
+    that boundary runs the preact=False sequence.  Inside a stage the raw
+    tensor is needed as the residual, so identity blocks keep the prologue.
 
     conv="miopen": MIOpen convolutions + the fused NHWC epilogues of
     vgpu.ops.fused (3 activation passes per bottleneck instead of 7).
@@ -156,11 +167,12 @@ class FusedResNetV2Inference(nn.Module):
     (tests/test_gpu_fused.py, tests/test_gpu_conv.py).
     """
 
-    def __init__(self, m: ResNetV2, conv: str = "native"):
+    def __init__(self, m: ResNetV2, conv: str = "native", preact: bool = True):
         super().__init__()
         if conv not in ("native", "miopen"):
             raise ValueError(conv)
         self.conv = conv
+        self.preact = preact
         # conv2+conv3 fusion (VGPU_FUSE_TAIL=0 disables, for A/B)
         import os
         self.fuse_tail = os.environ.get("VGPU_FUSE_TAIL", "1") != "0"
@@ -206,24 +218,43 @@ class FusedResNetV2Inference(nn.Module):
     def _forward_native(self, x: torch.Tensor) -> torch.Tensor:
         from vgpu.ops import conv as C
         x = x.contiguous(memory_format=torch.channels_last)
-        x = C.stem_pool(x, self.stem_w_s2d)  # stem conv + max pool, one kernel
-        x = self._blocks_native(x, 0, len(self.blocks))
+        X = C.stem_space_to_depth(x)
+        # stem conv + max pool, one kernel; pre-activated for block 0 where the kernel takes the shape
+        x, pre = _maybe_post(functools.partial(C.stem_pool_s2d, X, self.stem_w_s2d), self._post_for(0))
+        x, _ = self._blocks_native(x, 0, len(self.blocks), pre)
         return self.fc(C.scale_shift_relu_mean(x, *self.out_ss))
 
-    def _blocks_native(self, x: torch.Tensor, first: int, last: int) -> torch.Tensor:
+    def _post_for(self, i: int):
+        """Block i's entry BN+ReLU for its producer's post epilogue: only a
+        projection block's input has no other reader."""
+        if not self.preact or i >= len(self.blocks) or self.blocks[i]["sc"] is None:
+            return None
+        return self.blocks[i]["in"]
+
+    def _blocks_native(self, x: torch.Tensor, first: int, last: int, pre: bool = False):
         """Blocks [first, last); `last` must start a stage (or be the end) so no
-        fused next-block conv1 output crosses the boundary."""
+        fused next-block conv1 output crosses the boundary.
+
+        Enters: block `first`'s input -- raw, or (pre=True, a projection block
+        only) already through that block's entry BN+ReLU.  Leaves: (tensor,
+        pre) for block `last` in the same sense; the tensor is raw only where
+        its producer has no post form for the shape or, at the end of the
+        network, where the final BN+ReLU+mean kernel reads it."""
         from vgpu.ops import conv as C
         h_next = None
         for i in range(first, last):
             b = self.blocks[i]
-            pro = b["in"]
+            # On a pre-activated input the two convs keep the prologue form's
+            # single-pass K order (it never runs split-K): same logits either way.
+            pro = None if pre else b["in"]
             if b["sc"] is None:
                 sc = x
             else:
-                sc = C.conv2d(x, b["sc"][0], stride=b["sc"][1], pro=pro)
-            h = h_next if h_next is not None else C.conv2d(x, b["w1"], b["b1"], act="relu", pro=pro)
+                sc = C.conv2d(x, b["sc"][0], stride=b["sc"][1], pro=pro, splitk=not pre)
+            h = h_next if h_next is not None else C.conv2d(x, b["w1"], b["b1"], act="relu", pro=pro,
+                                                           splitk=not pre)
             h_next = None
+            pre = False
             nb = self.blocks[i + 1] if i + 1 < last else None
             if (self.fuse_next and nb is not None and nb["sc"] is None
                     and C.conv23_supported(h.shape[1])):
@@ -232,11 +263,12 @@ class FusedResNetV2Inference(nn.Module):
                                       stride=b["stride"])
             elif self.fuse_tail and C.conv23_supported(h.shape[1]):
                 # conv2 + conv3 + residual in one kernel (stages 1-2)
-                x = C.conv23(h, b["w2"], b["b2"], b["w3"], sc, stride=b["stride"])
+                x, pre = _maybe_post(functools.partial(C.conv23, h, b["w2"], b["b2"], b["w3"], sc,
+                                                       stride=b["stride"]), self._post_for(i + 1))
             else:
                 h = C.conv2d(h, b["w2"], b["b2"], stride=b["stride"], padding=1, act="relu")
-                x = C.conv2d(h, b["w3"], residual=sc)
-        return x
+                x, pre = _maybe_post(functools.partial(C.conv2d, h, b["w3"], residual=sc), self._post_for(i + 1))
+        return x, pre
 
     def _forward_miopen(self, x: torch.Tensor) -> torch.Tensor:
         from vgpu.ops.fused import add_scale_shift_act, bias_act_, scale_shift_act
@@ -256,6 +288,13 @@ class FusedResNetV2Inference(nn.Module):
             x, pre = add_scale_shift_act(h, sc, *nss)
         pooled = pre.mean(dim=(2, 3))
         return self.fc(pooled)
+
+
+def _maybe_post(op, post):
+    """(op(post=post), True) where the op has a post form for its shape (an op
+    answers None, having launched nothing, where it has not), else (op(), False)."""
+    y = op(post=post) if post is not None else None
+    return (y, True) if y is not None else (op(), False)
 
 
 def resnet_v2_50(num_classes: int = 1000) -> ResNetV2:

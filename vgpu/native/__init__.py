@@ -90,6 +90,14 @@ def load_kernels() -> ctypes.CDLL:
     lib.vgpu_conv_set_splitk.argtypes = [ci]
     lib.vgpu_maxpool_nhwc.argtypes = [vp, vp] + [ci] * 7 + [vp]
     lib.vgpu_stem_pool_nhwc.argtypes = [vp, vp, vp] + [ci] * 3 + [vp]
+    # "post" epilogue producers (the next projection block's entry BN+ReLU stored in place of y)
+    lib.vgpu_stem_pool_post_nhwc.argtypes = [vp] * 5 + [ci] * 3 + [vp]
+    lib.vgpu_stem_pool_post_nhwc.restype = ci
+    lib.vgpu_conv23_post_nhwc.argtypes = [vp] * 8 + [ci] * 5 + [vp]
+    lib.vgpu_conv23_post_nhwc.restype = ci
+    lib.vgpu_conv2d_post_nhwc_ws.argtypes = [vp] * 6 + [ci] * 6 + [vp, ctypes.c_int64, vp]
+    lib.vgpu_conv2d_post_nhwc_ws.restype = ci
+    lib.vgpu_conv_set_tile_m.argtypes = [ci]
     lib.vgpu_conv_set_big.argtypes = [ci]
     lib.vgpu_conv_set_halo.argtypes = [ci]
     lib.vgpu_conv_halo_launches.restype = ctypes.c_ulonglong

@@ -3,6 +3,11 @@
 
     y = act(conv(pro(x), w) + bias + residual),   pro(x) = relu(x * scale[c] + shift[c])
 
+Producers of a tensor that only a projection block reads (stem_pool, conv23,
+the 1x1 + residual conv2d) take post=(scale, shift): they store pro(y) in place
+of y, rounded as the consumers' prologue would round it, and that block's
+shortcut and conv1 then run without a prologue on identical operands.
+
 Tensors: bf16, NCHW-shaped, channels_last memory.  Supported: 1x1 and 3x3
 filters, any stride / padding, C % 64 == 0 and Cout % 64 == 0 (every
 convolution of ResNet-V2 after the stem), plus the narrow 4x4 C=16 form the
@@ -52,12 +57,19 @@ _ACTS = {"none": 0, "relu": 1, "relu6": 2}  # the kernels' epilogue activation c
 def conv2d(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None = None, *,
            stride: int = 1, padding: int = 0, act: str = "none",
            pro: tuple[torch.Tensor, torch.Tensor] | None = None,
-           residual: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+           residual: torch.Tensor | None = None, out: torch.Tensor | None = None,
+           post: tuple[torch.Tensor, torch.Tensor] | None = None, splitk: bool = True) -> torch.Tensor | None:
     """x [N,C,H,W] bf16 channels_last; w [Cout,C,k,k] bf16 channels_last;
     bias fp32 or bf16 [Cout]; pro = (scale, shift) fp32 [C] (BN+ReLU on the input);
     residual [N,Cout,OH,OW] bf16 channels_last; act 'none' | 'relu' | 'relu6'.
     Convs whose output tiles cannot fill the GPU run split-K (a workspace from
-    the caching allocator, vgpu_conv2d_workspace)."""
+    the caching allocator, vgpu_conv2d_workspace); splitk=False keeps the
+    single-pass K order (a conv on a pre-activated input then sums exactly as
+    the prologue form of the same conv, which never splits).
+    post = (scale, shift) fp32 [Cout]: relu(y * scale + shift) is stored in
+    place of y -- a 1x1 conv + residual only (no bias, act or pro).  With post
+    the result is None, and nothing was launched, when no kernel with that
+    epilogue takes the shape: the caller runs the conv without it."""
     _nhwc(x, "x")
     _nhwc(w, "w")
     n, c, h, wd = x.shape
@@ -77,6 +89,10 @@ def conv2d(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None = None, *
         raise ValueError("bias size")
     if pro is not None and (pro[0].numel() != c or pro[1].numel() != c):
         raise ValueError("prologue size")
+    if post is not None:
+        if ks != 1 or padding != 0 or residual is None or bias is not None or act != "none" or pro is not None:
+            raise ValueError("post: a 1x1 conv + residual without bias, act or pro")
+        _check_post(post, cout)
     if residual is not None:
         _nhwc(residual, "residual")
         if tuple(residual.shape) != (n, cout, oh, ow):
@@ -87,10 +103,18 @@ def conv2d(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None = None, *
         _nhwc(out, "out")
     lib = load_kernels()
     key = (n, h, wd, c, cout, ks, stride, padding, pro is not None)
-    need = _WS_BYTES.get(key)
+    need = _WS_BYTES.get(key) if splitk else 0
     if need is None:
         need = _WS_BYTES[key] = lib.vgpu_conv2d_workspace(*key[:-1], int(pro is not None))
     ws = torch.empty(need // 4, dtype=torch.float32, device=x.device) if need > 0 else None
+    if post is not None:
+        rc = lib.vgpu_conv2d_post_nhwc_ws(_ptr(x), _ptr(w), _ptr(out), _ptr(residual), _ptr(post[0]), _ptr(post[1]),
+                                          n, h, wd, c, cout, stride, _ptr(ws), need, _stream())
+        if rc == -1:
+            return None
+        if rc != 0:
+            raise RuntimeError(f"vgpu_conv2d_post_nhwc_ws: error {rc}")
+        return out
     code = _ACTS[act] | (256 if bias is not None and bias.dtype == torch.bfloat16 else 0)
     rc = lib.vgpu_conv2d_nhwc_ws(
         _ptr(x), _ptr(w), _ptr(out), _ptr(residual), _ptr(bias),
@@ -104,6 +128,12 @@ def conv2d(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None = None, *
 _WS_BYTES: dict[tuple, int] = {}  # conv shape -> split-K workspace bytes (0: unsplit)
 
 
+def _check_post(post: tuple[torch.Tensor, torch.Tensor], cout: int) -> None:
+    for p in post:
+        if p.dtype != torch.float32 or not p.is_contiguous() or not p.is_cuda or p.numel() != cout:
+            raise TypeError(f"post parameters must be contiguous fp32 CUDA tensors of size {cout}")
+
+
 def set_splitk(mode: int) -> None:
     """A/B switch for split-K: -1 heuristic (default), 0 off, n > 1 that many
     splits wherever eligible."""
@@ -112,8 +142,11 @@ def set_splitk(mode: int) -> None:
 
 
 def conv23(x: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, w3: torch.Tensor,
-           residual: torch.Tensor, *, stride: int = 1, out: torch.Tensor | None = None) -> torch.Tensor:
+           residual: torch.Tensor, *, stride: int = 1, out: torch.Tensor | None = None,
+           post: tuple[torch.Tensor, torch.Tensor] | None = None) -> torch.Tensor | None:
     """Fused bottleneck tail: y = conv1x1(relu(conv3x3(x, w2, stride, pad 1) + b2), w3) + residual.
+    post = (scale, shift) fp32 [4W]: relu(y * scale + shift) is stored in place
+    of y; None (nothing launched) if the native side does not take it.
 
     x [N,W,H,Wd] with W ∈ {64, 128}; w2 [W,W,3,3]; b2 fp32 [W]; w3 [4W,W,1,1];
     residual [N,4W,OH,OW].  The conv2 activation stays on-chip (native/kernels/conv_gemm.hip,
@@ -133,6 +166,15 @@ def conv23(x: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, w3: torch.Tensor
         raise ValueError("residual shape")
     if out is None:
         out = torch.empty((n, 4 * c, oh, ow), dtype=x.dtype, device=x.device, memory_format=_CL)
+    if post is not None:
+        _check_post(post, 4 * c)
+        rc = load_kernels().vgpu_conv23_post_nhwc(_ptr(x), _ptr(w2), _ptr(b2), _ptr(w3), _ptr(residual), _ptr(out),
+                                                  _ptr(post[0]), _ptr(post[1]), n, h, wd, c, stride, _stream())
+        if rc == -1:
+            return None
+        if rc != 0:
+            raise RuntimeError(f"vgpu_conv23_post_nhwc: error {rc}")
+        return out
     rc = load_kernels().vgpu_conv23_nhwc(_ptr(x), _ptr(w2), _ptr(b2), _ptr(w3), _ptr(residual), _ptr(out),
                                          n, h, wd, c, stride, _stream())
     if rc != 0:
@@ -222,17 +264,37 @@ def stem_conv(x: torch.Tensor, w_s2d: torch.Tensor, k: int = 7, pad: int = 3) ->
     return conv2d(stem_space_to_depth(x, k, pad), w_s2d)
 
 
-def stem_pool(x: torch.Tensor, w_s2d: torch.Tensor, k: int = 7, pad: int = 3) -> torch.Tensor:
+def stem_pool(x: torch.Tensor, w_s2d: torch.Tensor, k: int = 7, pad: int = 3,
+              post: tuple[torch.Tensor, torch.Tensor] | None = None) -> torch.Tensor | None:
     """maxpool3s2(stem_conv(x, w_s2d)) in one kernel (the stem activation never
     reaches HBM); bit-identical to the two-kernel path, which it falls back to
-    for shapes the fused kernel does not take (stem rows wider than 176)."""
-    X = stem_space_to_depth(x, k, pad)
+    for shapes the fused kernel does not take (stem rows wider than 176).
+    post: see stem_pool_s2d."""
+    return stem_pool_s2d(stem_space_to_depth(x, k, pad), w_s2d, post=post)
+
+
+def stem_pool_s2d(X: torch.Tensor, w_s2d: torch.Tensor,
+                  post: tuple[torch.Tensor, torch.Tensor] | None = None) -> torch.Tensor | None:
+    """stem_pool on the space-to-depth input X = stem_space_to_depth(x).
+    post = (scale, shift) fp32 [64]: relu(y * scale + shift) is stored in place
+    of y, by the fused kernel only -- where that one does not take the shape the
+    result is None and nothing was launched."""
     n, _, hs, ws = X.shape
+    if post is not None:
+        _check_post(post, w_s2d.shape[0])
     if w_s2d.shape[0] != 64:
-        return maxpool3s2(conv2d(X, w_s2d))
+        return None if post is not None else maxpool3s2(conv2d(X, w_s2d))
     oh, ow = hs - 3, ws - 3
     ph, pw = out_hw(oh, ow, 3, 2, 1)
-    out = torch.empty((n, 64, ph, pw), dtype=x.dtype, device=x.device, memory_format=_CL)
+    out = torch.empty((n, 64, ph, pw), dtype=X.dtype, device=X.device, memory_format=_CL)
+    if post is not None:
+        rc = load_kernels().vgpu_stem_pool_post_nhwc(_ptr(X), _ptr(w_s2d), _ptr(out), _ptr(post[0]), _ptr(post[1]),
+                                                     n, hs, ws, _stream())
+        if rc == -1:
+            return None
+        if rc != 0:
+            raise RuntimeError(f"vgpu_stem_pool_post_nhwc: error {rc}")
+        return out
     rc = load_kernels().vgpu_stem_pool_nhwc(_ptr(X), _ptr(w_s2d), _ptr(out), n, hs, ws, _stream())
     if rc == -1:
         return maxpool3s2(conv2d(X, w_s2d))
