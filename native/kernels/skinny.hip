@@ -137,11 +137,21 @@ struct SgdJob {
   int nesterov, first;
 };
 
-constexpr int kDgRows = 256;  // rows per block (64 per wave); 128 rows or 16 loads in flight ran no faster
-// The SGD form writes as much as it reads: 128 rows x 4 loads in flight ran VGG-16 b=2 at
-// 1 591-1 610 images/s against 1 563-1 572 for 256 x 8 / 256 x 4, 1 600-1 604 for 128 x 8, 1 581-1 588 for
-// 128 x 2, 1 588-1 601 for 64 x 8 / 64 x 4 and 1 554 for 32 x 4 (profiles/r5/train).
+// Rows per block (32 per wave).  The SGD form writes as much as it reads: 128 rows x 4 loads
+// in flight ran VGG-16 b=2 at 1 591-1 610 images/s against 1 563-1 572 for 256 x 8 / 256 x 4,
+// 1 600-1 604 for 128 x 8, 1 581-1 588 for 128 x 2, 1 588-1 601 for 64 x 8 / 64 x 4 and 1 554
+// for 32 x 4 (profiles/r5/train).
+// The plain form MUST split the rows alike: dx is a sum over rows, per wave in row order,
+// then over the four waves, then over the blocks, and only the same partition makes the
+// fused backward's dx bit-identical to the unfused one.  (The plain form ran 256 rows at
+// first; the two then rounded a few bf16 elements of dx differently per step from batch 3
+// up: tests/test_optim.py::test_sgd_in_skinny_backward_bit_exact.)  Loads in flight do not
+// enter the order.  On MI355X at 128 against 256 rows, batch 2: the data gradient alone 43.6
+// vs 40.2 us for fc1 (4096 x 25088), 17.9 vs 16.2 for 4096 x 4096, 8.3 vs 10.5 for 1000 x
+// 4096; the whole backward, with the split sum's loads unrolled below, 76.0 vs 76.0, 20.6 vs
+// 25.2 and 10.3 vs 13.8 us (batch 8, 4096 x 4096: 68.6 vs 80.6).
 constexpr int kSgdRows = 128;
+constexpr int kDgRows = kSgdRows;
 // bf16(gg) -> SGD on one weight element (sgd_bf16_kernel's math)
 __device__ __forceinline__ void sgd_elem(const SgdJob& sj, float gg, float& p, float& m) {
   gg = fmaf(sj.wd, p, gg);
@@ -303,6 +313,8 @@ __global__ void __launch_bounds__(kThreads) skinny_wgrad_kernel(const uint16_t* 
          i += (int64_t)gridDim.x * kThreads) {
       const float4* p = reinterpret_cast<const float4*>(job.ws) + i * 2;
       float4 a = p[0], b = p[1];
+      // four splits' loads in flight; the additions stay in split order
+#pragma unroll 4
       for (int sp = 1; sp < job.splits; ++sp) {
         const float4* q = p + (int64_t)sp * job.total8 * 2;
         const float4 c = q[0], d = q[1];

@@ -155,11 +155,17 @@ def test_fuse_into_backward_registers_linear_weights_cpu():
         assert torch.equal(p, q)
 
 
+_SGD_KW = [dict(lr=0.1, momentum=0.9), dict(lr=0.05, momentum=0.9, weight_decay=1e-2),
+           dict(lr=0.05, momentum=0.8, nesterov=True), dict(lr=0.1, momentum=0.9, dampening=0.3)]
+# batch 2 keeps its ids (kw0..kw3); the other instantiated batches follow (the
+# kernel's static LDS, red[3][B][64][9] + sg[B][128], is largest at 8)
+_SGD_CASES = [pytest.param(kw, 2, id=f"kw{i}") for i, kw in enumerate(_SGD_KW)] + [
+    pytest.param(kw, b, id=f"kw{i}-b{b}") for b in (1, 3, 4, 8) for i, kw in enumerate(_SGD_KW)]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("kw", [dict(lr=0.1, momentum=0.9), dict(lr=0.05, momentum=0.9, weight_decay=1e-2),
-                                dict(lr=0.05, momentum=0.8, nesterov=True),
-                                dict(lr=0.1, momentum=0.9, dampening=0.3)])
-def test_sgd_in_skinny_backward_bit_exact(gpu_build, kw):
+@pytest.mark.parametrize("kw,bsz", _SGD_CASES)
+def test_sgd_in_skinny_backward_bit_exact(gpu_build, kw, bsz):
     """native/kernels/skinny.hip SgdJob: the FC weights stepped inside their
     backward give the same bf16 weights, momentum buffers and input gradient
     as the unfused native SGD over a materialised dW, over four steps (the
@@ -169,8 +175,8 @@ def test_sgd_in_skinny_backward_bit_exact(gpu_build, kw):
     opts = [SGD(n.parameters(), **kw) for n in nets]
     assert opts[1].fuse_into_backward(nets[1]) == 2
     torch.manual_seed(1)
-    xs = [torch.randn(2, 1032, device="cuda", dtype=torch.bfloat16) for _ in range(4)]
-    dys = [torch.randn(2, 200, device="cuda", dtype=torch.bfloat16) for _ in range(4)]
+    xs = [torch.randn(bsz, 1032, device="cuda", dtype=torch.bfloat16) for _ in range(4)]
+    dys = [torch.randn(bsz, 200, device="cuda", dtype=torch.bfloat16) for _ in range(4)]
     for net, opt in zip(nets, opts):
         net.dx = []
         for x, dy in zip(xs, dys):
