@@ -1741,7 +1741,9 @@ hipError_t dispatch_pro(const ConvArgs& a, bool res, hipStream_t s) {
 // memory, for the same reason.
 // POST: that p is stored in place of y (the post epilogue: the next block is a
 // projection block, nobody reads y itself); pv is not written.
-template <int BM, int BN, bool NEXT, int NT = kThreads, bool POST = false, typename Mid>
+// RES = false: no residual operand (conv23's shortcut-in-tail form has already
+// added it to the accumulators); res is not read.
+template <int BM, int BN, bool NEXT, int NT = kThreads, bool POST = false, bool RES = true, typename Mid>
 __device__ __forceinline__ void tail_epilogue(const ConvArgs& a, f32x4_t (&acc)[BM / (NT / 128) / 16][BN / 32],
                                               int m0, int n0, char* smem,
                                               const u32x4 (&res)[2][EpiShape<BM, BN, NT>::RROWS],
@@ -1790,10 +1792,15 @@ __device__ __forceinline__ void tail_epilogue(const ConvArgs& a, f32x4_t (&acc)[
       const int r = rfirst + E::RSTEP * i;
       const float4 c0 = *reinterpret_cast<const float4*>(sC + r * CS + chunk * 8);
       const float4 c1 = *reinterpret_cast<const float4*>(sC + r * CS + chunk * 8 + 4);
-      float re[8];
-      unpack8(res[h][i], re);
-      v[i][0] = c0.x + re[0]; v[i][1] = c0.y + re[1]; v[i][2] = c0.z + re[2]; v[i][3] = c0.w + re[3];
-      v[i][4] = c1.x + re[4]; v[i][5] = c1.y + re[5]; v[i][6] = c1.z + re[6]; v[i][7] = c1.w + re[7];
+      if constexpr (RES) {
+        float re[8];
+        unpack8(res[h][i], re);
+        v[i][0] = c0.x + re[0]; v[i][1] = c0.y + re[1]; v[i][2] = c0.z + re[2]; v[i][3] = c0.w + re[3];
+        v[i][4] = c1.x + re[4]; v[i][5] = c1.y + re[5]; v[i][6] = c1.z + re[6]; v[i][7] = c1.w + re[7];
+      } else {
+        v[i][0] = c0.x; v[i][1] = c0.y; v[i][2] = c0.z; v[i][3] = c0.w;
+        v[i][4] = c1.x; v[i][5] = c1.y; v[i][6] = c1.z; v[i][7] = c1.w;
+      }
     }
     if (h == 1) {
       __builtin_amdgcn_s_waitcnt(kLgkm0);
@@ -1854,7 +1861,17 @@ __device__ __forceinline__ void tail_epilogue(const ConvArgs& a, f32x4_t (&acc)[
 // workgroup per CU); the tails are latency-, not L2-bandwidth-bound.
 // POST: the block ends a stage -- its output is stored through the post
 // epilogue (ConvArgs::qscale of b, staged in LDS like NEXT's parameters).
-template <int BM, int W, bool NEXT = false, int NS1 = 3, int NT = kThreads, bool POST = false>
+// SC: the block's 1x1 / stride-1 projection shortcut (K = 64: block 0 of a
+// ResNet-V2) is computed here, not read back as a residual.  b.res is then the
+// shortcut's input x' [M][64] (b.res_bytes its extent) and b.bnx its weights
+// [4W][64].  Per conv3 chunk, x' (BM rows) and the chunk's 128 weight rows are
+// DMA'd into the epilogue staging area, idle until the chunk's MFMAs are done;
+// the shortcut GEMM runs first into accumulators of its own, is rounded to bf16
+// where the stand-alone conv stores it, and that value is added in fp32 to the
+// conv3 accumulators before they are staged -- the same roundings and the same
+// fp32 addition as residual = conv(x', wsc), so y and h1 are bit-identical,
+// without the shortcut's 4W-wide write and re-read.
+template <int BM, int W, bool NEXT = false, int NS1 = 3, int NT = kThreads, bool POST = false, bool SC = false>
 __global__ void __launch_bounds__(NT, 512 / NT) conv23_kernel(const ConvArgs a, const ConvArgs b,
                                                               const ConvArgs c) {
   constexpr int KCH = W / 64;                // conv3 K chunks (64 channels each)
@@ -1879,6 +1896,8 @@ __global__ void __launch_bounds__(NT, 512 / NT) conv23_kernel(const ConvArgs a, 
   constexpr int PAR = (W + (NEXT || POST ? 8 * W : 0)) * 4;
   static_assert(P + PAR <= 160 * 1024, "conv23: LDS");
   static_assert(NT == 512 || 2 * (P + PAR) <= 160 * 1024, "conv23: two workgroups per CU");
+  static_assert(!SC || (NEXT && W == 64), "shortcut in the tail: K = 64, behind the fused conv1");
+  static_assert(!SC || (BM + BN2) * 128 <= EPI, "shortcut operands fit the epilogue staging area");
   __shared__ __attribute__((aligned(16))) char smem[P + PAR];
   char* sA2 = smem + B2_BYTES + EPI;
   float* sPar = reinterpret_cast<float*>(smem + P);
@@ -1988,6 +2007,12 @@ __global__ void __launch_bounds__(NT, 512 / NT) conv23_kernel(const ConvArgs a, 
   // stores are unconditional, so their count is exact.  w1 goes through
   // registers because hipcc drains every in-flight LDS-DMA at the next
   // ds_write, and the epilogue and the A3 image are all ds_writes.
+  // SC: no residual loads.  w3(ch), x' and wsc(ch) are three DMA groups issued
+  // together (chunk 0: behind the A image; later: behind the conv1 barrier) and
+  // all waited for with vmcnt(0) at the chunk's start; the only global loads
+  // consumed from registers are w1's, and no DMA is in flight behind them.
+  //   wait · shortcut MMA (staging area) → bf16 · conv3 MMA · += shortcut ·
+  //   barrier (staging area and panel read out) · epilogue as NEXT, no residual
   using E2 = EpiShape<BM, 128, NT>;
   constexpr int R = 2 * E2::RROWS;  // residual loads = y stores per thread per chunk
   constexpr int WTM2 = BM / WGM, TM2 = WTM2 / 16;
@@ -2003,11 +2028,32 @@ __global__ void __launch_bounds__(NT, 512 / NT) conv23_kernel(const ConvArgs a, 
             w3r, (lds_void_t*)(sB2 + kc * (BN2 * 128) + (RPI * i + wave * 8) * 128), 16,
             (uint32_t)(((ch * BN2 + lrow + RPI * i) * b.K + kc * 64 + lchunk * 8) * 2), 0, 0, 0);
   };
+  // SC: x' rows of this tile and the shortcut weight rows of chunk ch, both in
+  // the swizzled K = 64 image mma_k64 reads, into the staging area.  Issued with
+  // w3(ch) and waited for with it; no residual load exists in this form.
+  const __amdgpu_buffer_rsrc_t xpr = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<uint16_t*>(b.res), 0, SC ? b.res_bytes : 0u, 0x00020000);
+  const __amdgpu_buffer_rsrc_t wscr = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<uint16_t*>(b.bnx), 0, SC ? (uint32_t)(b.Cout * 64 * 2) : 0u, 0x00020000);
+  auto issue_sc = [&](int ch) {
+#pragma unroll
+    for (int i = 0; i < BM / RPI; ++i) {
+      const int m = m0 + lrow + RPI * i;
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(
+          xpr, (lds_void_t*)(sE + (RPI * i + wave * 8) * 128), 16,
+          m < b.M ? (uint32_t)((m * 64 + lchunk * 8) * 2) : kOOB, 0, 0, 0);
+    }
+#pragma unroll
+    for (int i = 0; i < BN2 / RPI; ++i)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(
+          wscr, (lds_void_t*)(sE + BM * 128 + (RPI * i + wave * 8) * 128), 16,
+          (uint32_t)(((ch * BN2 + lrow + RPI * i) * 64 + lchunk * 8) * 2), 0, 0, 0);
+  };
   u32x4 res[2][E2::RROWS];
   // res(0) flies while the conv2 tile is turned into conv3's A image; w3(0)
   // goes into the (free) phase-1 stages after that image's ds_writes, which
   // would otherwise drain it.
-  load_residual<BM, BN2, false, NT>(b, m0, 0, res);
+  if constexpr (!SC) load_residual<BM, BN2, false, NT>(b, m0, 0, res);
 
   // conv2 bias + ReLU → bf16 → conv3's A image: lane (fr, fk) of subtile (i, j)
   // holds row i*16+fr (+wave offset), channels j*16+fk*4 .. +3.
@@ -2027,6 +2073,7 @@ __global__ void __launch_bounds__(NT, 512 / NT) conv23_kernel(const ConvArgs a, 
   }
 
   issue_w3(0);
+  if constexpr (SC) issue_sc(0);
 
   // phase 3 (NEXT): conv1 of the next block, W outputs per row, K = 4W
   constexpr int TM3 = BM / WGM / 16, TN3 = W / 32;
@@ -2044,14 +2091,32 @@ __global__ void __launch_bounds__(NT, 512 / NT) conv23_kernel(const ConvArgs a, 
     const int c0 = ch * BN2;
     // w3(ch) landed; res(ch) may fly, and without NEXT the previous chunk's
     // second-half stores (issued after w3(ch), behind the epilogue's last ds_write)
-    if (ch == 0)
-      __builtin_amdgcn_s_waitcnt(vmcnt_imm(0));  // res(0) was issued before w3(0)
+    if (ch == 0 || SC)
+      __builtin_amdgcn_s_waitcnt(vmcnt_imm(0));  // res(0) was issued before w3(0); SC: w3, x' and wsc, no res
     else if (NEXT)
       __builtin_amdgcn_s_waitcnt(vmcnt_imm(R));
     else
       __builtin_amdgcn_s_waitcnt(vmcnt_imm(R + R / 2));
     __builtin_amdgcn_s_waitcnt(kLgkm0);
     __builtin_amdgcn_s_barrier();  // B2 visible; A2 written (first chunk); previous staging read out
+    // SC: the shortcut GEMM first, held packed as bf16 (its stored form) so
+    // its fp32 accumulators are dead before acc2 is live.
+    uint32_t scp[SC ? TM2 : 1][TN2][2];
+    if constexpr (SC) {
+      f32x4_t accs[TM2][TN2];
+#pragma unroll
+      for (int i = 0; i < TM2; ++i)
+#pragma unroll
+        for (int j = 0; j < TN2; ++j) accs[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+      mma_k64<TM2, TN2>(sE, sE + BM * 128, wm * WTM2, wn * 64, fr, fk, accs);
+#pragma unroll
+      for (int i = 0; i < TM2; ++i)
+#pragma unroll
+        for (int j = 0; j < TN2; ++j) {
+          scp[i][j][0] = pack2(accs[i][j][0], accs[i][j][1]);
+          scp[i][j][1] = pack2(accs[i][j][2], accs[i][j][3]);
+        }
+    }
     f32x4_t acc2[TM2][TN2];
 #pragma unroll
     for (int i = 0; i < TM2; ++i)
@@ -2060,6 +2125,17 @@ __global__ void __launch_bounds__(NT, 512 / NT) conv23_kernel(const ConvArgs a, 
 #pragma unroll
     for (int kc = 0; kc < KCH; ++kc)
       mma_k64<TM2, TN2>(sA2 + kc * (BM * 128), sB2 + kc * (BN2 * 128), wm * WTM2, wn * 64, fr, fk, acc2);
+    if constexpr (SC) {
+#pragma unroll
+      for (int i = 0; i < TM2; ++i)
+#pragma unroll
+        for (int j = 0; j < TN2; ++j) {
+          acc2[i][j][0] += __uint_as_float(scp[i][j][0] << 16);
+          acc2[i][j][1] += __uint_as_float(scp[i][j][0] & 0xffff0000u);
+          acc2[i][j][2] += __uint_as_float(scp[i][j][1] << 16);
+          acc2[i][j][3] += __uint_as_float(scp[i][j][1] & 0xffff0000u);
+        }
+    }
     // res(ch) landed before any DMA is issued behind it (hipcc would otherwise
     // drain that DMA at the residual's first use); B2 read out by every wave
     // before the next DMA overwrites it.
@@ -2084,7 +2160,7 @@ __global__ void __launch_bounds__(NT, 512 / NT) conv23_kernel(const ConvArgs a, 
         for (int i = 0; i < W / RPI; ++i)
           w1v[kc][i] = __builtin_amdgcn_raw_buffer_load_b128(
               w1r, (uint32_t)(((lrow + RPI * i) * c.K + c0 + kc * 64 + (t & 7) * 8) * 2), 0, 0);
-      tail_epilogue<BM, BN2, true, NT>(b, acc2, m0, c0, sE, res, sPar + W, sPar + 5 * W, pv, [] {});
+      tail_epilogue<BM, BN2, true, NT, false, !SC>(b, acc2, m0, c0, sE, res, sPar + W, sPar + 5 * W, pv, [] {});
       // A3 image (BM rows x 128 channels = two 64-wide swizzled panels) in the
       // staging area, which the epilogue has finished reading.
       {
@@ -2112,7 +2188,10 @@ __global__ void __launch_bounds__(NT, 512 / NT) conv23_kernel(const ConvArgs a, 
       __builtin_amdgcn_s_barrier();  // A3 / weight chunk read before the next chunk reuses them
       if (ch + 1 < nchunks) {
         issue_w3(ch + 1);
-        load_residual<BM, BN2, false, NT>(b, m0, c0 + BN2, res);
+        if constexpr (SC)
+          issue_sc(ch + 1);
+        else
+          load_residual<BM, BN2, false, NT>(b, m0, c0 + BN2, res);
       }
     }
   }
@@ -2512,9 +2591,13 @@ VGPU_API unsigned long long vgpu_conv_halo_launches() { return g_halo_launches; 
 static int conv23_impl(const void* x, const void* w2, const float* b2, const void* w3, const void* res,
                        void* y, const void* w1n, const float* b1n, const float* psn, const float* ptn,
                        void* h1n, int N, int H, int W, int C, int stride, hipStream_t s,
-                       const float* qs = nullptr, const float* qt = nullptr) {
-  if ((C != 64 && C != 128) || stride < 1 || N < 1 || !b2 || !res) return -1;
+                       const float* qs = nullptr, const float* qt = nullptr, const void* xpre = nullptr,
+                       const void* wsc = nullptr) {
+  // xpre/wsc (both, in place of res): the shortcut-in-tail form, y = conv3 + bf16(xpre · wscᵀ).
+  const bool sc = xpre != nullptr;
+  if ((C != 64 && C != 128) || stride < 1 || N < 1 || !b2 || (res == nullptr) == !sc) return -1;
   const bool next = w1n != nullptr, post = qs != nullptr;
+  if (sc && (!wsc || !next || C != 64 || stride != 1)) return -1;
   if (next && (!b1n || !psn || !ptn || !h1n)) return -1;
   if ((qs == nullptr) != (qt == nullptr) || (post && next)) return -1;
   ConvArgs a{};
@@ -2532,7 +2615,8 @@ static int conv23_impl(const void* x, const void* w2, const float* b2, const voi
   ConvArgs b{};
   b.w = static_cast<const uint16_t*>(w3);
   b.y = static_cast<uint16_t*>(y);
-  b.res = static_cast<const uint16_t*>(res);
+  b.res = static_cast<const uint16_t*>(sc ? xpre : res);
+  b.bnx = static_cast<const uint16_t*>(wsc);
   b.Cout = 4 * C;
   b.K = C;
   b.qscale = qs;
@@ -2562,7 +2646,8 @@ static int conv23_impl(const void* x, const void* w2, const float* b2, const voi
     c.M = nb * a.OH * a.OW;
     d.M = c.M;
     d.y = b.y + (int64_t)n0 * (yi / 2);
-    d.res = b.res + (int64_t)n0 * (yi / 2);
+    d.res = b.res + (int64_t)n0 * ((sc ? xi : yi) / 2);  // sc: x' is [N][H][W][64], as large as x
+    d.res_bytes = (uint32_t)(nb * xi);
     d.y_bytes = (uint32_t)(nb * yi);
     if (next) {
       e.M = c.M;
@@ -2572,7 +2657,10 @@ static int conv23_impl(const void* x, const void* w2, const float* b2, const voi
     const int bm = C == 64 ? 128 : 64;
     c.nM = (c.M + bm - 1) / bm; c.nN = 1; c.nwg = c.nM;
     if (C == 64) {
-      if (next)
+      if (sc)
+        hipLaunchKernelGGL((conv23_kernel<128, 64, true, 3, kThreads, false, true>), dim3(c.nwg), dim3(kThreads), 0,
+                           s, c, d, e);
+      else if (next)
         hipLaunchKernelGGL((conv23_kernel<128, 64, true>), dim3(c.nwg), dim3(kThreads), 0, s, c, d, e);
       else if (post)
         hipLaunchKernelGGL((conv23_kernel<128, 64, false, 3, kThreads, true>), dim3(c.nwg), dim3(kThreads), 0, s, c,
@@ -2620,6 +2708,21 @@ VGPU_API int vgpu_conv231_nhwc(const void* x, const void* w2, const float* b2, c
                                int C, int stride, hipStream_t s) {
   if (!w1n) return -1;
   return conv23_impl(x, w2, b2, w3, res, y, w1n, b1n, psn, ptn, h1n, N, H, W, C, stride, s);
+}
+
+// vgpu_conv231_nhwc whose residual is the block's own projection shortcut,
+// computed in the kernel: y = conv3(...) + bf16(conv1x1(xpre, wsc)) with xpre
+// [N][H][W][Csc] the block input as the shortcut reads it (pre-activated) and
+// wsc [4C][Csc].  Bit-identical to passing that conv's output as res.  Takes
+// C = 64, Csc = 64, stride 1 (block 0 of a ResNet-V2); -1, nothing launched,
+// for anything else.
+VGPU_API int vgpu_conv231_sc_nhwc(const void* x, const void* w2, const float* b2, const void* w3,
+                                  const void* xpre, const void* wsc, void* y, const void* w1n,
+                                  const float* b1n, const float* psn, const float* ptn, void* h1n, int N,
+                                  int H, int W, int C, int Csc, int stride, hipStream_t s) {
+  if (!w1n || !xpre || !wsc || C != 64 || Csc != 64 || stride != 1) return -1;
+  return conv23_impl(x, w2, b2, w3, nullptr, y, w1n, b1n, psn, ptn, h1n, N, H, W, C, stride, s, nullptr, nullptr,
+                     xpre, wsc);
 }
 
 namespace {

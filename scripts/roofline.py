@@ -10,7 +10,8 @@ CPU only: the plan is derived from the model's layer shapes, mirroring the
 dispatch decisions of `_forward_native` (conv23/conv231 fusion for C in
 {64, 128}; separate conv2/conv3 otherwise; the input of a projection block
 stored pre-activated by its producer, so that block's shortcut and conv1 carry
-no prologue -- same bytes and FLOPs either way).  `--measured-ms` is the bench's
+no prologue -- same bytes and FLOPs either way; block 0's stride-1 shortcut
+computed inside its fused tail, one row).  `--measured-ms` is the bench's
 ms_per_step (all pods) to compare against.
 """
 from __future__ import annotations
@@ -58,7 +59,11 @@ def plan(batch: int, size: int, layers=(3, 4, 6, 3)):
         m_in = batch * h * h
         ho = conv_out(h, 3, stride, 1)
         m_out = batch * ho * ho
-        if proj:
+        nxt = blocks[bi + 1] if bi + 1 < len(blocks) else None
+        # block 0: the stride-1, K = 64 projection shortcut runs inside the fused tail
+        # (conv23_kernel<128, 64, NEXT, SC>); its output is neither written nor read back
+        sc_in_tail = proj and stride == 1 and ci == 64 and wd == 64 and nxt is not None and not nxt[3]
+        if proj and not sc_in_tail:
             out.append((f"b{bi} shortcut 1x1 (pre-activated input)", 2 * m_out * ci * co,
                         E * (m_in * ci + m_out * co + ci * co)))
         if not h_next_ready:
@@ -66,11 +71,17 @@ def plan(batch: int, size: int, layers=(3, 4, 6, 3)):
             kind = "pre-activated input" if proj else "BN+ReLU prologue"
             out.append((f"b{bi} conv1 1x1 ({kind})", 2 * m_in * ci * wd, E * (m_in * ci + m_in * wd + ci * wd)))
         h_next_ready = False
-        nxt = blocks[bi + 1] if bi + 1 < len(blocks) else None
         f2 = 2 * m_out * 9 * wd * wd
         f3 = 2 * m_out * wd * co
         w23 = E * (9 * wd * wd + wd * co)
-        if wd in (64, 128) and nxt is not None and not nxt[3]:
+        if sc_in_tail:
+            # the shortcut row and the tail row in one: the shortcut's FLOPs, its input and
+            # weights; of the tail's two 4W-wide passes (residual in, y out) only y is left
+            f1n = 2 * m_out * co * nxt[1]
+            out.append((f"b{bi} shortcut+conv2+conv3+next conv1", 2 * m_out * ci * co + f2 + f3 + f1n,
+                        E * (m_in * ci + ci * co + m_in * wd + m_out * co + m_out * nxt[1] + co * nxt[1]) + w23))
+            h_next_ready = True
+        elif wd in (64, 128) and nxt is not None and not nxt[3]:
             f1n = 2 * m_out * co * nxt[1]
             out.append((f"b{bi} conv2+conv3+res+next conv1", f2 + f3 + f1n,
                         E * (m_in * wd + m_out * co * 2 + m_out * nxt[1] + co * nxt[1]) + w23))

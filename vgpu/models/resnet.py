@@ -160,6 +160,11 @@ class FusedResNetV2Inference(nn.Module):
     that boundary runs the preact=False sequence.  Inside a stage the raw
     tensor is needed as the residual, so identity blocks keep the prologue.
 
+    fuse_sc (default on; VGPU_FUSE_SC=0): block 0's stride-1 projection shortcut
+    is computed inside its conv2+conv3(+next conv1) kernel from the pre-activated
+    stem output, so its 4x-wide result is neither written nor read back; logits
+    are bit-identical to fuse_sc=False.  Needs preact and the fused next conv1.
+
     conv="miopen": MIOpen convolutions + the fused NHWC epilogues of
     vgpu.ops.fused (3 activation passes per bottleneck instead of 7).
 
@@ -167,7 +172,7 @@ class FusedResNetV2Inference(nn.Module):
     (tests/test_gpu_fused.py, tests/test_gpu_conv.py).
     """
 
-    def __init__(self, m: ResNetV2, conv: str = "native", preact: bool = True):
+    def __init__(self, m: ResNetV2, conv: str = "native", preact: bool = True, fuse_sc: bool | None = None):
         super().__init__()
         if conv not in ("native", "miopen"):
             raise ValueError(conv)
@@ -178,6 +183,9 @@ class FusedResNetV2Inference(nn.Module):
         self.fuse_tail = os.environ.get("VGPU_FUSE_TAIL", "1") != "0"
         # ... and the next identity block's conv1 into that tail (VGPU_FUSE_NEXT=0 disables)
         self.fuse_next = self.fuse_tail and os.environ.get("VGPU_FUSE_NEXT", "1") != "0"
+        # ... and a stride-1 projection shortcut (block 0) computed inside that tail on the
+        # pre-activated input, its output never stored (VGPU_FUSE_SC=0 or fuse_sc=False disables)
+        self.fuse_sc = (os.environ.get("VGPU_FUSE_SC", "1") != "0") if fuse_sc is None else bool(fuse_sc)
         from vgpu.ops.fused import bn_scale_shift
         m = m.eval()
         dt = m.stem.weight.dtype
@@ -247,17 +255,33 @@ class FusedResNetV2Inference(nn.Module):
             # On a pre-activated input the two convs keep the prologue form's
             # single-pass K order (it never runs split-K): same logits either way.
             pro = None if pre else b["in"]
+            nb = self.blocks[i + 1] if i + 1 < last else None
+            next_ok = (self.fuse_next and nb is not None and nb["sc"] is None
+                       and C.conv23_supported(b["w2"].shape[0]))
+            # A stride-1 projection shortcut on a pre-activated input (block 0) is
+            # computed inside the fused tail, never stored
+            sc_in_tail = (self.fuse_sc and next_ok and pre and b["sc"] is not None and b["sc"][1] == 1
+                          and b["stride"] == 1)
             if b["sc"] is None:
                 sc = x
+            elif sc_in_tail:
+                sc = None
             else:
                 sc = C.conv2d(x, b["sc"][0], stride=b["sc"][1], pro=pro, splitk=not pre)
             h = h_next if h_next is not None else C.conv2d(x, b["w1"], b["b1"], act="relu", pro=pro,
                                                            splitk=not pre)
             h_next = None
+            if sc_in_tail:
+                out = C.conv231(h, b["w2"], b["b2"], b["w3"], None, nb["w1"], nb["b1"], nb["in"],
+                                shortcut=(x, b["sc"][0]))
+                if out is not None:
+                    x, h_next = out
+                    pre = False
+                    continue
+                # the native side does not take the shape (nothing launched): the separate shortcut conv
+                sc = C.conv2d(x, b["sc"][0], stride=1, splitk=False)
             pre = False
-            nb = self.blocks[i + 1] if i + 1 < last else None
-            if (self.fuse_next and nb is not None and nb["sc"] is None
-                    and C.conv23_supported(h.shape[1])):
+            if next_ok:
                 # conv2 + conv3 + residual + the next block's BN+ReLU+conv1 (stages 1-2)
                 x, h_next = C.conv231(h, b["w2"], b["b2"], b["w3"], sc, nb["w1"], nb["b1"], nb["in"],
                                       stride=b["stride"])

@@ -97,6 +97,9 @@ def load_kernels() -> ctypes.CDLL:
     lib.vgpu_conv23_post_nhwc.restype = ci
     lib.vgpu_conv2d_post_nhwc_ws.argtypes = [vp] * 6 + [ci] * 6 + [vp, ctypes.c_int64, vp]
     lib.vgpu_conv2d_post_nhwc_ws.restype = ci
+    # conv231 with block 0's projection shortcut computed in the kernel (xpre, wsc in place of res)
+    lib.vgpu_conv231_sc_nhwc.argtypes = [vp] * 12 + [ci] * 6 + [vp]
+    lib.vgpu_conv231_sc_nhwc.restype = ci
     lib.vgpu_conv_set_tile_m.argtypes = [ci]
     lib.vgpu_conv_set_big.argtypes = [ci]
     lib.vgpu_conv_set_halo.argtypes = [ci]

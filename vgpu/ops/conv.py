@@ -183,13 +183,27 @@ def conv23(x: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, w3: torch.Tensor
 
 
 def conv231(x: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, w3: torch.Tensor,
-            residual: torch.Tensor, w1n: torch.Tensor, b1n: torch.Tensor,
-            pro_n: tuple[torch.Tensor, torch.Tensor], *, stride: int = 1) -> tuple[torch.Tensor, torch.Tensor]:
+            residual: torch.Tensor | None, w1n: torch.Tensor, b1n: torch.Tensor,
+            pro_n: tuple[torch.Tensor, torch.Tensor], *, stride: int = 1,
+            shortcut: tuple[torch.Tensor, torch.Tensor] | None = None
+            ) -> tuple[torch.Tensor, torch.Tensor] | None:
     """conv23 plus the next identity-shortcut block's conv1 in one kernel:
     y = conv23(x, ...) (the next block's input, still stored as its residual) and
     h1n = relu(conv1x1(relu(y*s + t), w1n) + b1n) with (s, t) = pro_n.  Numerics
-    equal conv23 followed by conv2d(y, w1n, b1n, act='relu', pro=pro_n)."""
+    equal conv23 followed by conv2d(y, w1n, b1n, act='relu', pro=pro_n).
+
+    shortcut = (xpre, wsc) in place of residual (which must then be None): the
+    residual is the block's own 1x1 projection shortcut conv2d(xpre, wsc),
+    computed inside the kernel and never stored -- bit-identical to passing
+    residual=conv2d(xpre, wsc, splitk=False).  xpre [N,Csc,OH,OW] is the block
+    input as the shortcut reads it (pre-activated), wsc [4W,Csc,1,1].  The
+    native side takes W = 64, Csc = 64, stride 1 (block 0 of a ResNet-V2); for
+    anything else the result is None and nothing was launched."""
     _nhwc(x, "x")
+    if (residual is None) == (shortcut is None):
+        raise ValueError("conv231 takes either residual or shortcut=(xpre, wsc)")
+    if shortcut is not None:
+        return _conv231_sc(x, w2, b2, w3, shortcut, w1n, b1n, pro_n, stride)
     for t, nm in ((w2, "w2"), (w3, "w3"), (residual, "residual"), (w1n, "w1n")):
         _nhwc(t, nm)
     n, c, h, wd = x.shape
@@ -209,6 +223,33 @@ def conv231(x: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, w3: torch.Tenso
                                           n, h, wd, c, stride, _stream())
     if rc != 0:
         raise RuntimeError(f"vgpu_conv231_nhwc: error {rc}")
+    return y, h1
+
+
+def _conv231_sc(x, w2, b2, w3, shortcut, w1n, b1n, pro_n, stride):
+    xpre, wsc = shortcut
+    for t, nm in ((w2, "w2"), (w3, "w3"), (xpre, "xpre"), (wsc, "wsc"), (w1n, "w1n")):
+        _nhwc(t, nm)
+    n, c, h, wd = x.shape
+    csc = xpre.shape[1]
+    if (c not in (64, 128) or tuple(w2.shape) != (c, c, 3, 3) or tuple(w3.shape) != (4 * c, c, 1, 1)
+            or tuple(w1n.shape) != (c, 4 * c, 1, 1) or tuple(wsc.shape) != (4 * c, csc, 1, 1)):
+        raise ValueError(f"unsupported fused tail + shortcut: x {tuple(x.shape)} wsc {tuple(wsc.shape)}")
+    for p_, nm, size in ((b2, "b2", c), (b1n, "b1n", c), (pro_n[0], "scale", 4 * c), (pro_n[1], "shift", 4 * c)):
+        if p_.dtype != torch.float32 or not p_.is_contiguous() or p_.numel() != size:
+            raise TypeError(f"{nm} must be a contiguous fp32 tensor of size {size}")
+    oh, ow = out_hw(h, wd, 3, stride, 1)
+    if stride == 1 and tuple(xpre.shape) != (n, csc, oh, ow):
+        raise ValueError("shortcut input shape")
+    y = torch.empty((n, 4 * c, oh, ow), dtype=x.dtype, device=x.device, memory_format=_CL)
+    h1 = torch.empty((n, c, oh, ow), dtype=x.dtype, device=x.device, memory_format=_CL)
+    rc = load_kernels().vgpu_conv231_sc_nhwc(_ptr(x), _ptr(w2), _ptr(b2), _ptr(w3), _ptr(xpre), _ptr(wsc), _ptr(y),
+                                             _ptr(w1n), _ptr(b1n), _ptr(pro_n[0]), _ptr(pro_n[1]), _ptr(h1),
+                                             n, h, wd, c, csc, stride, _stream())
+    if rc == -1:
+        return None
+    if rc != 0:
+        raise RuntimeError(f"vgpu_conv231_sc_nhwc: error {rc}")
     return y, h1
 
 
