@@ -37,6 +37,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "conv_plan.h"
+
 #define VGPU_API extern "C" __attribute__((visibility("default")))
 
 namespace {
@@ -112,13 +114,8 @@ __device__ __forceinline__ float bn_act_grad(int act, float z) {
   return 1.0f;
 }
 
-__device__ __forceinline__ float bf2f(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
 // Keep `v` in a VGPR as it is here (no rematerialisation, no hoisting past this point).
 __device__ __forceinline__ void pin_vgpr(uint32_t& v) { asm volatile("" : "+v"(v)); }
-__device__ __forceinline__ uint16_t f2bf(float f) {
-  __bf16 b = (__bf16)f;
-  return __builtin_bit_cast(uint16_t, b);
-}
 
 __device__ __forceinline__ void unpack8(const u32x4 v, float (&f)[8]) {
   f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
@@ -193,7 +190,7 @@ constexpr uint32_t kOOB = 0x80000000u;  // buffer offset past num_records: loads
 // branching around loads (a branch around a load makes it wait vmcnt(0) and
 // de-pipelines the loop).  The residual of a tile is fetched in its last K step,
 // issued before that step's A/B prefetch so the epilogue waits only for it.
-template <int KS, int BM, int BN, bool PRO, bool RES>
+template <int KS, int BM, int BN, bool RES>
 __global__ void __launch_bounds__(kThreads, 2) conv_gemm_kernel(const ConvArgs a) {
   constexpr int AR = BM * 8 / kThreads;  // 16-B A chunks per thread per K step
   constexpr int BR = BN * 8 / kThreads;
@@ -276,23 +273,21 @@ __global__ void __launch_bounds__(kThreads, 2) conv_gemm_kernel(const ConvArgs a
   {                                                                                          \
     char* sA = smem + (st_) * STAGE;                                                         \
     char* sB = sA + A_BYTES;                                                                 \
-    if constexpr (PRO) {                                                                     \
-      const int c = ((kt_) % a.cblocks) * BK + slot * 8;                                     \
-      const float4 s0 = *reinterpret_cast<const float4*>(a.pscale + c);                     \
-      const float4 s1 = *reinterpret_cast<const float4*>(a.pscale + c + 4);                  \
-      const float4 h0 = *reinterpret_cast<const float4*>(a.pshift + c);                     \
-      const float4 h1 = *reinterpret_cast<const float4*>(a.pshift + c + 4);                  \
-      const float sc[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};                  \
-      const float sh[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};                  \
-      _Pragma("unroll") for (int i = 0; i < AR; ++i) {                                       \
-        float e[8];                                                                          \
-        unpack8(RA[i], e);                                                                   \
-        _Pragma("unroll") for (int j = 0; j < 8; ++j) {                                      \
-          const float f = fmaxf(e[j] * sc[j] + sh[j], 0.0f);                                 \
-          e[j] = RV[i] ? f : 0.0f;                                                           \
-        }                                                                                    \
-        RA[i] = pack8(e);                                                                    \
+    const int c = ((kt_) % a.cblocks) * BK + slot * 8;                                       \
+    const float4 s0 = *reinterpret_cast<const float4*>(a.pscale + c);                       \
+    const float4 s1 = *reinterpret_cast<const float4*>(a.pscale + c + 4);                    \
+    const float4 h0 = *reinterpret_cast<const float4*>(a.pshift + c);                       \
+    const float4 h1 = *reinterpret_cast<const float4*>(a.pshift + c + 4);                    \
+    const float sc[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};                    \
+    const float sh[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};                    \
+    _Pragma("unroll") for (int i = 0; i < AR; ++i) {                                         \
+      float e[8];                                                                            \
+      unpack8(RA[i], e);                                                                     \
+      _Pragma("unroll") for (int j = 0; j < 8; ++j) {                                        \
+        const float f = fmaxf(e[j] * sc[j] + sh[j], 0.0f);                                   \
+        e[j] = RV[i] ? f : 0.0f;                                                             \
       }                                                                                      \
+      RA[i] = pack8(e);                                                                      \
     }                                                                                        \
     _Pragma("unroll") for (int i = 0; i < AR; ++i)                                           \
       *reinterpret_cast<u32x4*>(sA + swz(r0 + 32 * i, slot)) = RA[i];                        \
@@ -910,7 +905,6 @@ __global__ void __launch_bounds__(kThreads) splitk_reduce_kernel(const ConvArgs 
 // The epilogue goes through a per-wave LDS slab in four 32-row quarters so
 // every store is a 16-B bf16x8 and the bias is loaded once per lane.
 constexpr int kBigThreads = 512;
-int conv_cus();
 
 
 // K steps of 32 (BK32) in an NS-deep ring of 32 KB LDS stages (NS = 4: 128 KB),
@@ -1084,15 +1078,6 @@ __global__ void __launch_bounds__(kBigThreads, 1) conv_big_kernel(const ConvArgs
     }
     __builtin_amdgcn_s_waitcnt(kLgkm0);  // slab read out before the next pass overwrites it
   }
-}
-
-template <bool RES>
-hipError_t launch_big(ConvArgs a, hipStream_t s) {
-  a.nM = (a.M + 255) / 256;
-  a.nN = a.Cout / 256;
-  a.nwg = a.nM * a.nN;
-  hipLaunchKernelGGL((conv_big_kernel<RES, 4>), dim3(a.nwg), dim3(kBigThreads), 0, s, a);
-  return hipGetLastError();
 }
 
 // ---- 3x3 / stride-1 convs from a halo tile in LDS ----------------------------
@@ -1413,86 +1398,6 @@ __global__ void __launch_bounds__(BM * BN / 64, 2) conv_halo_kernel(const ConvAr
   }
 }
 
-int g_forced_halo = -1;  // vgpu_conv_set_halo: -1 = env VGPU_CONV_HALO, 0 = off, 1 = on, 2 / 3 = on with BM 256 / 128
-
-bool halo_enabled() {
-  static int on = -1;
-  if (on < 0) {
-    const char* v = getenv("VGPU_CONV_HALO");
-    on = (v && (v[0] == '0' || v[0] == 'n' || v[0] == 'f')) ? 0 : 1;
-  }
-  return on == 1;
-}
-
-unsigned long long g_halo_launches = 0;  // vgpu_conv_halo_launches (tests: the halo path ran)
-
-template <int BM, int BN, int HPMAX>
-hipError_t launch_halo(ConvArgs a, hipStream_t s) {
-  ++g_halo_launches;
-  a.nM = (a.M + BM - 1) / BM;
-  a.nN = a.Cout / BN;
-  a.nwg = a.nM * a.nN;
-  // N-major placement when the filter outgrows an XCD's L2 share (4 MiB).
-  a.nmajor = (int64_t)a.Cout * a.K * 2 > ((int64_t)5 << 19) ? 1 : 0;
-  if (a.stats && a.bnx)
-    hipLaunchKernelGGL((conv_halo_kernel<BM, BN, HPMAX, 2>), dim3(a.nwg), dim3(BM * BN / 64), 0, s, a);
-  else if (a.stats)
-    hipLaunchKernelGGL((conv_halo_kernel<BM, BN, HPMAX, 1>), dim3(a.nwg), dim3(BM * BN / 64), 0, s, a);
-  else
-    hipLaunchKernelGGL((conv_halo_kernel<BM, BN, HPMAX>), dim3(a.nwg), dim3(BM * BN / 64), 0, s, a);
-  return hipGetLastError();
-}
-
-// Halo pixels a BM-pixel tile of a W-wide image can need: rows spanned + 2.
-inline int halo_pixels(int bm, int w) { return ((bm - 1) / w + 4) * w; }
-
-// 3x3 / stride 1 / pad 1, no prologue / residual, Cout % 128 == 0.  Returns
-// hipErrorNotSupported when no halo instantiation fits (the caller falls back).
-hipError_t dispatch_halo(const ConvArgs& a, hipStream_t s) {
-  if (a.Cout % 128) return hipErrorNotSupported;
-  const int64_t tiles256 = (int64_t)((a.M + 255) / 256) * (a.Cout / 128);
-  const bool big = g_forced_halo == 2 || (g_forced_halo != 3 && tiles256 * 5 >= (int64_t)conv_cus() * 3);
-  if (big && halo_pixels(256, a.W) <= 383) return launch_halo<256, 128, 384>(a, s);
-  if (g_forced_halo != 2 && halo_pixels(128, a.W) <= 191) return launch_halo<128, 128, 192>(a, s);
-  return hipErrorNotSupported;
-}
-
-int g_forced_big = -1;  // vgpu_conv_set_big: -1 = env VGPU_CONV_BIG / heuristic, 0 = off, 1 = whenever eligible
-
-int g_forced_bm = 0;  // vgpu_conv_set_tile_m (A/B benchmarking); 0 = heuristic
-
-template <int KS, int BM, int BN, bool RES, int CSM = 0, int ST = 0, bool POST = false>
-hipError_t launch_glds(ConvArgs a, hipStream_t s) {
-  a.nM = (a.M + BM - 1) / BM;
-  a.nN = a.Cout / BN;
-  a.nwg = a.nM * a.nN;
-  hipLaunchKernelGGL((conv_glds_kernel<KS, BM, BN, RES, CSM, ST, false, POST>), dim3(a.nwg), dim3(kThreads), 0, s,
-                     a);
-  return hipGetLastError();
-}
-
-// 1x1 + residual with the post epilogue (ConvArgs::qscale)
-template <int BM>
-hipError_t dispatch_glds_post(const ConvArgs& a, hipStream_t s) {
-  if (a.Cout % 128 == 0) return launch_glds<1, BM, 128, true, 0, 0, true>(a, s);
-  return launch_glds<1, BM, 64, true, 0, 0, true>(a, s);
-}
-
-template <int KS, int BM>
-hipError_t dispatch_glds(const ConvArgs& a, bool res, hipStream_t s) {
-  if (a.stats) {  // training BatchNorm statistics in the epilogue (backward: no residual)
-    const bool bwd = a.bnx != nullptr;
-    if (a.Cout % 128 == 0)
-      return bwd ? (res ? launch_glds<KS, BM, 128, true, 0, 2>(a, s) : launch_glds<KS, BM, 128, false, 0, 2>(a, s))
-                 : (res ? launch_glds<KS, BM, 128, true, 0, 1>(a, s) : launch_glds<KS, BM, 128, false, 0, 1>(a, s));
-    return bwd ? (res ? launch_glds<KS, BM, 64, true, 0, 2>(a, s) : launch_glds<KS, BM, 64, false, 0, 2>(a, s))
-               : (res ? launch_glds<KS, BM, 64, true, 0, 1>(a, s) : launch_glds<KS, BM, 64, false, 0, 1>(a, s));
-  }
-  if (a.Cout % 128 == 0)
-    return res ? launch_glds<KS, BM, 128, true>(a, s) : launch_glds<KS, BM, 128, false>(a, s);
-  return res ? launch_glds<KS, BM, 64, true>(a, s) : launch_glds<KS, BM, 64, false>(a, s);
-}
-
 // ---- Prologue convs (block-entry BN+ReLU on the input): A through registers,
 // B through LDS-DMA.
 //
@@ -1710,22 +1615,6 @@ __global__ void __launch_bounds__(kThreads, 2) conv_pro_kernel(const ConvArgs a)
   __syncthreads();
   if constexpr (RES) load_residual<BM, BN>(a, m0, n0, res);
   epilogue_halves<BM, BN, RES>(a, acc, m0, n0, smem, res);
-}
-
-template <int KS, int BM, int BN, bool RES>
-hipError_t launch_pro(ConvArgs a, hipStream_t s) {
-  a.nM = (a.M + BM - 1) / BM;
-  a.nN = a.Cout / BN;
-  a.nwg = a.nM * a.nN;
-  hipLaunchKernelGGL((conv_pro_kernel<KS, BM, BN, RES>), dim3(a.nwg), dim3(kThreads), 0, s, a);
-  return hipGetLastError();
-}
-
-template <int KS, int BM>
-hipError_t dispatch_pro(const ConvArgs& a, bool res, hipStream_t s) {
-  if (a.Cout % 128 == 0)
-    return res ? launch_pro<KS, BM, 128, true>(a, s) : launch_pro<KS, BM, 128, false>(a, s);
-  return res ? launch_pro<KS, BM, 64, true>(a, s) : launch_pro<KS, BM, 64, false>(a, s);
 }
 
 // conv23's conv3-chunk epilogue, one row half at a time: fp32 accumulators →
@@ -2240,49 +2129,110 @@ int conv_cus() {
 
 // A/B knob: 128-row tiles for non-prologue 1x1 convs too (VGPU_CONV_1X1_BIG=1).
 bool conv_1x1_big() {
-  static int on = -1;
-  if (on < 0) {
-    const char* v = getenv("VGPU_CONV_1X1_BIG");
-    on = (v && v[0] == '1') ? 1 : 0;
-  }
-  return on == 1;
+  static const char* const v = getenv("VGPU_CONV_1X1_BIG");
+  return v && v[0] == '1';
 }
 
-template <int KS, int BM, int BN, bool PRO, bool RES>
-hipError_t launch(ConvArgs a, hipStream_t s) {
-  static int occ = 0;  // resident workgroups per CU (LDS / VGPR bound); one value per instantiation
-  if (occ == 0) {
-    int o = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, conv_gemm_kernel<KS, BM, BN, PRO, RES>,
-                                                     kThreads, 0) != hipSuccess || o < 1)
-      o = 1;
-    occ = o;
-  }
+bool halo_enabled() {
+  static const char* const v = getenv("VGPU_CONV_HALO");
+  return !(v && (v[0] == '0' || v[0] == 'n' || v[0] == 'f'));
+}
+
+// ---- Host side: knobs → plan (conv_plan.h) → one launch ----------------------
+int g_forced_bm = 0;      // vgpu_conv_set_tile_m (A/B benchmarking); 0 = heuristic
+int g_forced_big = -1;    // vgpu_conv_set_big: -1 = env VGPU_CONV_BIG / heuristic, 0 = off, 1 = whenever eligible
+int g_forced_halo = -1;   // vgpu_conv_set_halo: -1 = env VGPU_CONV_HALO, 0 = off, 1 = on, 2 / 3 = on with BM 256 / 128
+int g_forced_split = -1;  // vgpu_conv_set_splitk: -1 heuristic, 0 off, n > 1 that many splits when eligible
+unsigned long long g_halo_launches = 0;  // vgpu_conv_halo_launches (tests: the halo path ran)
+
+convplan::ConvKnobs conv_knobs() {
+  const char* big = g_forced_big < 0 ? getenv("VGPU_CONV_BIG") : nullptr;
+  return {conv_cus(), g_forced_bm, g_forced_big, g_forced_halo, g_forced_split,
+          big ? (big[0] == '1' ? 1 : (big[0] == '0' ? 0 : 2)) : 2, halo_enabled(), conv_1x1_big()};
+}
+
+// CUs of the current device, whatever share of them this process owns.
+int device_cus() {
   int dev = 0, cus = 0;
-  (void)hipGetDevice(&dev);
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
     cus = 256;
-  a.nM = (a.M + BM - 1) / BM;
-  a.nN = a.Cout / BN;
-  a.nwg = a.nM * a.nN;
-  int grid = cus * occ;
-  grid = grid < 8 ? 8 : grid & ~7;  // multiple of 8: a workgroup keeps its XCD's tiles
-  if (a.nwg <= grid) grid = a.nwg;
-  hipLaunchKernelGGL((conv_gemm_kernel<KS, BM, BN, PRO, RES>), dim3(grid), dim3(kThreads), 0, s, a);
+  return cus;
+}
+
+using ConvKernel = void (*)(const ConvArgs);
+// K<KS, BM, BN, RES, more...> for KS 1 / 3, BM 64 / 128, BN 64 / 128, RES: a table [KS == 3][BM == 128][BN == 128][RES]
+#define VGPU_BN_RES(K, ks, bm, ...)                                            \
+  {{K<ks, bm, 64, false, ##__VA_ARGS__>, K<ks, bm, 64, true, ##__VA_ARGS__>}, \
+   {K<ks, bm, 128, false, ##__VA_ARGS__>, K<ks, bm, 128, true, ##__VA_ARGS__>}}
+#define VGPU_TILES(K, ...)                                                     \
+  {{VGPU_BN_RES(K, 1, 64, ##__VA_ARGS__), VGPU_BN_RES(K, 1, 128, ##__VA_ARGS__)}, \
+   {VGPU_BN_RES(K, 3, 64, ##__VA_ARGS__), VGPU_BN_RES(K, 3, 128, ##__VA_ARGS__)}}
+
+// The plan's kernel; every family's instantiations are listed here once.
+ConvKernel conv_kernel(const convplan::ConvPlan& p) {
+  using convplan::Family;
+  // gemm: the prologue convs that conv_pro_kernel does not take (K ≤ 2 steps,
+  // Cout == 64, C > 2048, a padded 1x1): A and B through registers, persistent grid.
+  static const ConvKernel reg[2][2][2][2][2] = {VGPU_TILES(conv_gemm_kernel), VGPU_TILES(conv_pro_kernel)};  // [pro]
+  static const ConvKernel glds[3][2][2][2][2] = {  // [ST]: training BatchNorm statistics in the epilogue
+      VGPU_TILES(conv_glds_kernel), VGPU_TILES(conv_glds_kernel, 0, 1), VGPU_TILES(conv_glds_kernel, 0, 2)};
+  static const ConvKernel split[2][2] = {  // [KS == 3][BN == 128]
+      {conv_glds_kernel<1, 64, 64, false, 0, 0, true>, conv_glds_kernel<1, 64, 128, false, 0, 0, true>},
+      {conv_glds_kernel<3, 64, 64, false, 0, 0, true>, conv_glds_kernel<3, 64, 128, false, 0, 0, true>}};
+  static const ConvKernel post[2][2] = {  // [BM == 128][BN == 128]: 1x1 + residual with the post epilogue
+      {conv_glds_kernel<1, 64, 64, true, 0, 0, false, true>, conv_glds_kernel<1, 64, 128, true, 0, 0, false, true>},
+      {conv_glds_kernel<1, 128, 64, true, 0, 0, false, true>, conv_glds_kernel<1, 128, 128, true, 0, 0, false, true>}};
+  static const ConvKernel narrow[2] = {conv_glds_kernel<4, 64, 64, false, 16>, conv_glds_kernel<4, 128, 64, false, 16>};
+  static const ConvKernel big[2] = {conv_big_kernel<false, 4>, conv_big_kernel<true, 4>};
+  static const ConvKernel halo[2][3] = {  // [BM == 256][ST]
+      {conv_halo_kernel<128, 128, 192>, conv_halo_kernel<128, 128, 192, 1>, conv_halo_kernel<128, 128, 192, 2>},
+      {conv_halo_kernel<256, 128, 384>, conv_halo_kernel<256, 128, 384, 1>, conv_halo_kernel<256, 128, 384, 2>}};
+  const int ks3 = p.KS == 3, bm128 = p.BM == 128, bn128 = p.BN == 128;
+  if (p.family == Family::big) return big[p.RES];
+  if (p.family == Family::halo) return halo[p.BM == 256][p.ST];
+  if (p.family != Family::glds) return reg[p.family == Family::pro][ks3][bm128][bn128][p.RES];
+  if (p.splits > 1) return split[ks3][bn128];
+  if (p.CSM) return narrow[bm128];
+  return p.POST ? post[bm128][bn128] : glds[p.ST][ks3][bm128][bn128][p.RES];
+}
+#undef VGPU_BN_RES
+#undef VGPU_TILES
+
+// conv23_kernel<BM, W, NEXT, 3, kThreads, POST, SC>, [W == 128][plain, next, post, next + sc]
+using Conv23Kernel = void (*)(const ConvArgs, const ConvArgs, const ConvArgs);
+const Conv23Kernel kConv23[2][4] = {
+    {conv23_kernel<128, 64>, conv23_kernel<128, 64, true>, conv23_kernel<128, 64, false, 3, kThreads, true>,
+     conv23_kernel<128, 64, true, 3, kThreads, false, true>},
+    {conv23_kernel<64, 128>, conv23_kernel<64, 128, true>, conv23_kernel<64, 128, false, 3, kThreads, true>, nullptr}};
+
+// The one launcher: tile counts from the plan, the plan's kernel on the plan's
+// grid, and the split-K reduce behind it when the plan splits.
+hipError_t launch_conv(ConvArgs a, const convplan::ConvPlan& p, hipStream_t s) {
+  const ConvKernel k = conv_kernel(p);
+  a.nM = p.nM; a.nN = p.nN; a.nwg = p.nM * p.nN; a.nmajor = p.nmajor;
+  int grid = a.nwg;
+  if (p.family == convplan::Family::gemm) {  // persistent: no more workgroups than stay resident
+    static int occupancy[2][2][2][2];  // resident workgroups per CU (LDS / VGPR bound), asked once per instantiation
+    int& occ = occupancy[p.KS == 3][p.BM == 128][p.BN == 128][p.RES];
+    if (occ == 0) {
+      int o = 0;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, k, kThreads, 0) != hipSuccess || o < 1) o = 1;
+      occ = o;
+    }
+    const int g = device_cus() * occ < 8 ? 8 : (device_cus() * occ) & ~7;  // of 8: a workgroup keeps its XCD's tiles
+    if (grid > g) grid = g;
+  }
+  if (p.family == convplan::Family::halo) ++g_halo_launches;
+  hipLaunchKernelGGL(k, dim3(grid, p.splits), dim3(p.threads), 0, s, a);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess || p.splits <= 1) return e;
+  const int64_t threads = (int64_t)a.M * (a.Cout / 8);
+  hipLaunchKernelGGL(p.POST ? splitk_reduce_kernel<true> : splitk_reduce_kernel<false>,
+                     dim3((unsigned)((threads + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, a);
   return hipGetLastError();
 }
 
-template <int KS, int BM, int BN>
-hipError_t dispatch_pr(const ConvArgs& a, bool pro, bool res, hipStream_t s) {
-  if (pro) return res ? launch<KS, BM, BN, true, true>(a, s) : launch<KS, BM, BN, true, false>(a, s);
-  return res ? launch<KS, BM, BN, false, true>(a, s) : launch<KS, BM, BN, false, false>(a, s);
-}
-
-template <int KS, int BM>
-hipError_t dispatch_bn(const ConvArgs& a, bool pro, bool res, hipStream_t s) {
-  if (a.Cout % 128 == 0) return dispatch_pr<KS, BM, 128>(a, pro, res, s);
-  return dispatch_pr<KS, BM, 64>(a, pro, res, s);
-}
 
 // ---- NHWC k x k max pool and fused BN+ReLU+global-average pool ----------------
 // One block per output row (grid OH x N): 32-bit index math only (the earlier
@@ -2583,28 +2533,45 @@ VGPU_API void vgpu_conv_set_big(int mode) { g_forced_big = mode; }  // -1 env/he
 VGPU_API void vgpu_conv_set_halo(int mode) { g_forced_halo = mode; }  // -1 env, 0 off, 1 on, 2/3 BM 256/128
 VGPU_API unsigned long long vgpu_conv_halo_launches() { return g_halo_launches; }
 
+namespace {
+// A vgpu_conv23* call: conv2 (a: x, w, bias, shape), conv3 (b: w, y, res; post: qscale / qshift; shortcut
+// in the tail: res = xpre, bnx = wsc) and the next block's conv1 (n: w, y = h1n, bias, pscale, pshift) or none.
+struct Conv23Args {
+  ConvArgs a{}, b{}, n{};
+};
+Conv23Args conv23_args(const void* x, const void* w2, const float* b2, const void* w3, const void* res, void* y, int N,
+                       int H, int W, int C, int stride) {
+  Conv23Args r;
+  r.a.x = static_cast<const uint16_t*>(x);
+  r.a.w = static_cast<const uint16_t*>(w2);
+  r.a.bias = b2;
+  r.a.N = N; r.a.H = H; r.a.W = W; r.a.C = C; r.a.Cout = C; r.a.stride = stride; r.a.pad = 1;
+  r.b.w = static_cast<const uint16_t*>(w3);
+  r.b.y = static_cast<uint16_t*>(y);
+  r.b.res = static_cast<const uint16_t*>(res);
+  return r;
+}
+void conv23_next(Conv23Args& r, const void* w1n, const float* b1n, const float* psn, const float* ptn, void* h1n) {
+  r.n.w = static_cast<const uint16_t*>(w1n);
+  r.n.y = static_cast<uint16_t*>(h1n);
+  r.n.bias = b1n; r.n.pscale = psn; r.n.pshift = ptn;
+}
+
 // Fused conv2 (3x3, pad 1, stride s, C = W → W, bias + ReLU) + conv3 (1x1,
 // W → 4W) + residual; with w1n, also the next block's conv1 (1x1, 4W → W,
 // prologue relu(y*ps + pt), bias b1n + ReLU) into h1n.  W ∈ {64, 128}.
 // qs/qt (both or neither, not with w1n): the post epilogue, y holds
 // relu(y·qs + qt) for the projection block that follows.
-static int conv23_impl(const void* x, const void* w2, const float* b2, const void* w3, const void* res,
-                       void* y, const void* w1n, const float* b1n, const float* psn, const float* ptn,
-                       void* h1n, int N, int H, int W, int C, int stride, hipStream_t s,
-                       const float* qs = nullptr, const float* qt = nullptr, const void* xpre = nullptr,
-                       const void* wsc = nullptr) {
-  // xpre/wsc (both, in place of res): the shortcut-in-tail form, y = conv3 + bf16(xpre · wscᵀ).
-  const bool sc = xpre != nullptr;
-  if ((C != 64 && C != 128) || stride < 1 || N < 1 || !b2 || (res == nullptr) == !sc) return -1;
-  const bool next = w1n != nullptr, post = qs != nullptr;
-  if (sc && (!wsc || !next || C != 64 || stride != 1)) return -1;
-  if (next && (!b1n || !psn || !ptn || !h1n)) return -1;
-  if ((qs == nullptr) != (qt == nullptr) || (post && next)) return -1;
-  ConvArgs a{};
-  a.x = static_cast<const uint16_t*>(x);
-  a.w = static_cast<const uint16_t*>(w2);
-  a.bias = b2;
-  a.N = N; a.H = H; a.W = W; a.C = C; a.Cout = C; a.stride = stride; a.pad = 1;
+int conv23_impl(const Conv23Args& r, hipStream_t s) {
+  ConvArgs a = r.a, b = r.b, cn = r.n;
+  // b.bnx (wsc): the shortcut-in-tail form, y = conv3 + bf16(xpre · wscᵀ) with xpre in place of res.
+  const bool sc = b.bnx != nullptr, next = cn.w != nullptr, post = b.qscale != nullptr;
+  const int N = a.N, H = a.H, W = a.W, C = a.C, stride = a.stride;
+  const int bm = convplan::conv23_bm(C, next, post, sc);
+  if (!bm || stride < 1 || N < 1 || !a.bias || !b.res || (sc && stride != 1)) return -1;
+  if (next && (!cn.bias || !cn.pscale || !cn.pshift || !cn.y)) return -1;
+  if ((b.qscale == nullptr) != (b.qshift == nullptr)) return -1;
+  const Conv23Kernel kern = kConv23[C == 128][sc ? 3 : next ? 1 : post ? 2 : 0];
   a.OH = (H + 2 - 3) / stride + 1;
   a.OW = (W + 2 - 3) / stride + 1;
   if (a.OH < 1 || a.OW < 1) return -1;
@@ -2612,26 +2579,9 @@ static int conv23_impl(const void* x, const void* w2, const float* b2, const voi
   a.cblocks = C / 64;
   a.ktiles = a.K / 64;
   a.act = 1;
-  ConvArgs b{};
-  b.w = static_cast<const uint16_t*>(w3);
-  b.y = static_cast<uint16_t*>(y);
-  b.res = static_cast<const uint16_t*>(sc ? xpre : res);
-  b.bnx = static_cast<const uint16_t*>(wsc);
   b.Cout = 4 * C;
   b.K = C;
-  b.qscale = qs;
-  b.qshift = qt;
-  ConvArgs cn{};
-  if (next) {
-    cn.w = static_cast<const uint16_t*>(w1n);
-    cn.y = static_cast<uint16_t*>(h1n);
-    cn.bias = b1n;
-    cn.pscale = psn;
-    cn.pshift = ptn;
-    cn.Cout = C;
-    cn.K = 4 * C;
-    cn.act = 1;
-  }
+  if (next) cn.Cout = C, cn.K = 4 * C, cn.act = 1;
   const int64_t xi = (int64_t)H * W * C * 2, yi = (int64_t)a.OH * a.OW * b.Cout * 2;
   const int64_t hi = (int64_t)a.OH * a.OW * C * 2;
   const int64_t lim = ((int64_t)1 << 31) - 1;
@@ -2654,38 +2604,19 @@ static int conv23_impl(const void* x, const void* w2, const float* b2, const voi
       e.y = cn.y + (int64_t)n0 * (hi / 2);
       e.y_bytes = (uint32_t)(nb * hi);
     }
-    const int bm = C == 64 ? 128 : 64;
     c.nM = (c.M + bm - 1) / bm; c.nN = 1; c.nwg = c.nM;
-    if (C == 64) {
-      if (sc)
-        hipLaunchKernelGGL((conv23_kernel<128, 64, true, 3, kThreads, false, true>), dim3(c.nwg), dim3(kThreads), 0,
-                           s, c, d, e);
-      else if (next)
-        hipLaunchKernelGGL((conv23_kernel<128, 64, true>), dim3(c.nwg), dim3(kThreads), 0, s, c, d, e);
-      else if (post)
-        hipLaunchKernelGGL((conv23_kernel<128, 64, false, 3, kThreads, true>), dim3(c.nwg), dim3(kThreads), 0, s, c,
-                           d, e);
-      else
-        hipLaunchKernelGGL((conv23_kernel<128, 64>), dim3(c.nwg), dim3(kThreads), 0, s, c, d, e);
-    } else {
-      if (next)
-        hipLaunchKernelGGL((conv23_kernel<64, 128, true>), dim3(c.nwg), dim3(kThreads), 0, s, c, d, e);
-      else if (post)
-        hipLaunchKernelGGL((conv23_kernel<64, 128, false, 3, kThreads, true>), dim3(c.nwg), dim3(kThreads), 0, s, c,
-                           d, e);
-      else
-        hipLaunchKernelGGL((conv23_kernel<64, 128>), dim3(c.nwg), dim3(kThreads), 0, s, c, d, e);
-    }
+    hipLaunchKernelGGL(kern, dim3(c.nwg), dim3(kThreads), 0, s, c, d, e);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) return (int)err;
   }
   return 0;
 }
+}  // namespace
 
 VGPU_API int vgpu_conv23_nhwc(const void* x, const void* w2, const float* b2, const void* w3,
                               const void* res, void* y, int N, int H, int W, int C, int stride,
                               hipStream_t s) {
-  return conv23_impl(x, w2, b2, w3, res, y, nullptr, nullptr, nullptr, nullptr, nullptr, N, H, W, C, stride, s);
+  return conv23_impl(conv23_args(x, w2, b2, w3, res, y, N, H, W, C, stride), s);
 }
 
 // vgpu_conv23_nhwc with the post epilogue: y = relu(bf16(conv23)·qs[c] + qt[c]),
@@ -2695,8 +2626,9 @@ VGPU_API int vgpu_conv23_post_nhwc(const void* x, const void* w2, const float* b
                                    const void* res, void* y, const float* qs, const float* qt, int N, int H,
                                    int W, int C, int stride, hipStream_t s) {
   if (!qs || !qt) return -1;
-  return conv23_impl(x, w2, b2, w3, res, y, nullptr, nullptr, nullptr, nullptr, nullptr, N, H, W, C, stride, s,
-                     qs, qt);
+  Conv23Args r = conv23_args(x, w2, b2, w3, res, y, N, H, W, C, stride);
+  r.b.qscale = qs; r.b.qshift = qt;
+  return conv23_impl(r, s);
 }
 
 // conv23 + the next (identity-shortcut) block's conv1 in one kernel: y is the
@@ -2707,7 +2639,9 @@ VGPU_API int vgpu_conv231_nhwc(const void* x, const void* w2, const float* b2, c
                                const float* psn, const float* ptn, void* h1n, int N, int H, int W,
                                int C, int stride, hipStream_t s) {
   if (!w1n) return -1;
-  return conv23_impl(x, w2, b2, w3, res, y, w1n, b1n, psn, ptn, h1n, N, H, W, C, stride, s);
+  Conv23Args r = conv23_args(x, w2, b2, w3, res, y, N, H, W, C, stride);
+  conv23_next(r, w1n, b1n, psn, ptn, h1n);
+  return conv23_impl(r, s);
 }
 
 // vgpu_conv231_nhwc whose residual is the block's own projection shortcut,
@@ -2721,65 +2655,92 @@ VGPU_API int vgpu_conv231_sc_nhwc(const void* x, const void* w2, const float* b2
                                   const float* b1n, const float* psn, const float* ptn, void* h1n, int N,
                                   int H, int W, int C, int Csc, int stride, hipStream_t s) {
   if (!w1n || !xpre || !wsc || C != 64 || Csc != 64 || stride != 1) return -1;
-  return conv23_impl(x, w2, b2, w3, nullptr, y, w1n, b1n, psn, ptn, h1n, N, H, W, C, stride, s, nullptr, nullptr,
-                     xpre, wsc);
+  Conv23Args r = conv23_args(x, w2, b2, w3, xpre, y, N, H, W, C, stride);
+  r.b.bnx = static_cast<const uint16_t*>(wsc);
+  conv23_next(r, w1n, b1n, psn, ptn, h1n);
+  return conv23_impl(r, s);
 }
 
 namespace {
-int conv2d_impl(const void* x, const void* w, void* y, const void* res, const float* bias, const float* pscale,
-                const float* pshift, int N, int H, int W, int C, int Cout, int KS, int stride, int pad, int act,
-                float* stats, const void* bnx, const float* bncoef, int bnact, int res_stride, hipStream_t s,
-                float* ws = nullptr, int64_t ws_bytes = 0, const void* gmask = nullptr, float* gpart = nullptr,
-                const void* pidx = nullptr, void* gfull = nullptr, int pk = 0, const float* qscale = nullptr,
-                const float* qshift = nullptr);
+// The operands every vgpu_conv2d_* entry point takes, as the ConvArgs that is
+// its request: the entry point adds its own operands field by field.
+ConvArgs conv_args(const void* x, const void* w, void* y, const void* res, int N, int H, int W, int C, int Cout,
+                   int stride, int pad) {
+  ConvArgs a{};
+  a.x = static_cast<const uint16_t*>(x);
+  a.w = static_cast<const uint16_t*>(w);
+  a.y = static_cast<uint16_t*>(y);
+  a.res = static_cast<const uint16_t*>(res);
+  a.N = N; a.H = H; a.W = W; a.C = C; a.Cout = Cout; a.stride = stride; a.pad = pad;
+  a.res_stride = 1;
+  return a;
+}
 
-int g_forced_split = -1;  // vgpu_conv_set_splitk: -1 heuristic, 0 off, n > 1 that many splits when eligible
+// Runs the request `a` (act bit 8: the bias is bf16).  Returns 0, a hipError_t,
+// or -1 for an unsupported conv: every batch slice is planned (conv_plan.h)
+// before the first launch, so -1 means nothing was launched.
+int conv2d_impl(ConvArgs a, int KS, int64_t ws_bytes, hipStream_t s) {
+  if ((a.pscale == nullptr) != (a.pshift == nullptr) || (a.qscale == nullptr) != (a.qshift == nullptr)) return -1;
+  a.bias_bf16 = (a.act >> 8) & 1;
+  a.act &= 0xff;
+  // The batch runs in slices of full.nb images; the last one may be shorter and has its own plan.
+  const convplan::ConvKnobs knobs = conv_knobs();
+  const convplan::ConvPlan full = convplan::conv_plan(a, KS, ws_bytes, knobs, false);
+  const convplan::ConvPlan last = convplan::conv_plan(a, KS, ws_bytes, knobs, true);
+  // VGPU_CONV_BIG is taken over by the first conv that gets to the unsplit kernels (until
+  // then it does not count as a forced knob for split-K); vgpu_conv_set_big(-1) re-reads it.
+  if (g_forced_big < 0 && (full.past_split() || last.past_split())) g_forced_big = knobs.env_big;
+  if (!full.ok() || !last.ok()) return -1;
+  const int N = a.N, Cout = a.Cout;
+  a.OH = convplan::out_size(a.H, KS, a.stride, a.pad);
+  a.OW = convplan::out_size(a.W, KS, a.stride, a.pad);
+  a.K = KS * KS * a.C;
+  a.cblocks = a.C / 64;
+  a.ktiles = a.K / 64;
+  a.res_h = (a.OH + 1) / 2; a.res_w = (a.OW + 1) / 2;
+  a.res_bytes = a.res_stride == 2 ? (uint32_t)((int64_t)N * a.res_h * a.res_w * Cout * 2) : 0;
+  const int64_t xi = (int64_t)a.H * a.W * a.C * 2, yi = (int64_t)a.OH * a.OW * Cout * 2;
+  for (int n0 = 0; n0 < N; n0 += full.nb) {
+    const convplan::ConvPlan& p = N - n0 < full.nb ? last : full;
+    ConvArgs c = a;
+    c.N = p.nb;
+    c.x = a.x + (int64_t)n0 * (xi / 2);
+    c.y = a.y + (int64_t)n0 * (yi / 2);
+    if (a.res) c.res = a.res + (int64_t)n0 * (yi / 2);
+    c.x_bytes = (uint32_t)(p.nb * xi);
+    c.y_bytes = (uint32_t)(p.nb * yi);
+    c.M = p.nb * a.OH * a.OW;
+    if (p.splits > 1) c.kper = p.kper, c.splits = p.splits;
+    else c.ws = nullptr;  // only a split launch gets the workspace
+    const hipError_t e = launch_conv(c, p, s);
+    if (e != hipSuccess) return (int)e;
+  }
+  return 0;
+}
 
-// Split-K for convs whose output tiles cannot fill the CUs this process owns:
-// the 28² / 14² layers of VGG-16 at batch 2 are 16-100 workgroups of 64x128 on
-// 256 CUs (36-41 us each, ~8 % of MFMA peak; profiles/r5/train).  The K steps
-// are cut into `splits` ranges so ~2 workgroups per CU run, each writing an
-// fp32 partial tile, and splitk_reduce_kernel applies the epilogue.  Returns
-// the split count (1 = no split) and the K steps per split.
-int splitk_plan(int64_t M, int C, int Cout, int KS, bool pro, bool narrow, int& kper) {
-  const int ktiles = KS * KS * C / 64;
-  kper = ktiles;
-  if (pro || narrow || C % 64 || (KS != 1 && KS != 3) || g_forced_split == 0) return 1;
-  // a kernel forced by an A/B or test setter runs as asked unless splits are forced too
-  if (g_forced_split < 0 && (g_forced_halo >= 0 || g_forced_big == 1 || g_forced_bm != 0)) return 1;
-  const int bn = Cout % 128 == 0 ? 128 : 64;
-  const int64_t tiles = ((M + 63) / 64) * (Cout / bn);
-  // Measured (profiles/r5/train/vgg_small_ab.log, graph replay): 100 and 28
-  // tiles gain 1.2-1.8x; 196 tiles (56² at b=2) lose 17 % -- split below half the CUs.
-  int64_t sp = g_forced_split > 1 ? g_forced_split : (2 * tiles >= conv_cus() ? 1 : 2 * (int64_t)conv_cus() / tiles);
-  if (sp > ktiles / 4) sp = ktiles / 4;
-  if (sp < 2) return 1;
-  kper = (int)((ktiles + sp - 1) / sp);
-  return (ktiles + kper - 1) / kper;
+// What both masked split-K entry points check and add to their request: false for -1.
+bool masked_args(ConvArgs& a, int KS, const void* gmask, void* gpart, int64_t gpart_bytes, void* ws, int* blocks_out) {
+  const int Cout = a.Cout;
+  if (!gmask || !gpart || !ws || Cout % 8 || kThreads % (Cout / 8) || KS < 1 || a.pad < 0) return false;
+  const int64_t OH = a.H + 2 * a.pad - KS + 1, OW = a.W + 2 * a.pad - KS + 1;
+  if (OH < 1 || OW < 1) return false;
+  const int64_t blocks = ((int64_t)a.N * OH * OW * (Cout / 8) + kThreads - 1) / kThreads;
+  if (convplan::conv_workspace(a.N, a.H, a.W, a.C, Cout, KS, 1, a.pad, false, conv_knobs()) <= 0 ||
+      gpart_bytes < blocks * Cout * 4)
+    return false;
+  if (blocks_out) *blocks_out = (int)blocks;
+  a.ws = static_cast<float*>(ws);
+  a.gmask = static_cast<const uint16_t*>(gmask);
+  a.gpart = static_cast<float*>(gpart);
+  return true;
 }
 }  // namespace
-
-// Returns 0, a hipError_t, or -1 for an unsupported shape (checked before any launch).
-VGPU_API int vgpu_conv2d_nhwc(const void* x, const void* w, void* y, const void* res,
-                              const float* bias, const float* pscale, const float* pshift, int N,
-                              int H, int W, int C, int Cout, int KS, int stride, int pad, int act,
-                              hipStream_t s) {
-  return conv2d_impl(x, w, y, res, bias, pscale, pshift, N, H, W, C, Cout, KS, stride, pad, act, nullptr,
-                     nullptr, nullptr, 0, 1, s);
-}
 
 // Workspace (bytes) vgpu_conv2d_nhwc_ws wants for a split-K launch of this
 // shape; 0 when the conv runs unsplit.
 VGPU_API int64_t vgpu_conv2d_workspace(int N, int H, int W, int C, int Cout, int KS, int stride, int pad,
                                        int has_pro) {
-  if (N < 1 || stride < 1 || pad < 0 || KS < 1) return 0;
-  const int64_t OH = (H + 2 * pad - KS) / stride + 1, OW = (W + 2 * pad - KS) / stride + 1;
-  if (OH < 1 || OW < 1) return 0;
-  const int64_t M = (int64_t)N * OH * OW;
-  const bool narrow = C == 16 && KS == 4 && stride == 1 && !has_pro;
-  int kper;
-  const int sp = splitk_plan(M, C, Cout, KS, has_pro != 0, narrow, kper);
-  return sp > 1 ? (int64_t)sp * M * Cout * 4 : 0;
+  return convplan::conv_workspace(N, H, W, C, Cout, KS, stride, pad, has_pro != 0, conv_knobs());
 }
 
 // vgpu_conv2d_nhwc with a split-K workspace (vgpu_conv2d_workspace bytes).
@@ -2787,8 +2748,19 @@ VGPU_API int64_t vgpu_conv2d_workspace(int N, int H, int W, int C, int Cout, int
 VGPU_API int vgpu_conv2d_nhwc_ws(const void* x, const void* w, void* y, const void* res, const void* bias,
                                  const float* pscale, const float* pshift, int N, int H, int W, int C, int Cout,
                                  int KS, int stride, int pad, int act, void* ws, int64_t ws_bytes, hipStream_t s) {
-  return conv2d_impl(x, w, y, res, static_cast<const float*>(bias), pscale, pshift, N, H, W, C, Cout, KS, stride,
-                     pad, act, nullptr, nullptr, nullptr, 0, 1, s, static_cast<float*>(ws), ws_bytes);
+  ConvArgs a = conv_args(x, w, y, res, N, H, W, C, Cout, stride, pad);
+  a.bias = static_cast<const float*>(bias); a.pscale = pscale; a.pshift = pshift; a.act = act;
+  a.ws = static_cast<float*>(ws);
+  return conv2d_impl(a, KS, ws_bytes, s);
+}
+
+// Returns 0, a hipError_t, or -1 for an unsupported shape (checked before any launch).
+VGPU_API int vgpu_conv2d_nhwc(const void* x, const void* w, void* y, const void* res,
+                              const float* bias, const float* pscale, const float* pshift, int N,
+                              int H, int W, int C, int Cout, int KS, int stride, int pad, int act,
+                              hipStream_t s) {
+  return vgpu_conv2d_nhwc_ws(x, w, y, res, bias, pscale, pshift, N, H, W, C, Cout, KS, stride, pad, act, nullptr, 0,
+                             s);
 }
 
 // vgpu_conv2d_nhwc_ws for a 1x1 conv + residual with the post epilogue:
@@ -2799,9 +2771,10 @@ VGPU_API int vgpu_conv2d_post_nhwc_ws(const void* x, const void* w, void* y, con
                                       const float* qt, int N, int H, int W, int C, int Cout, int stride, void* ws,
                                       int64_t ws_bytes, hipStream_t s) {
   if (!qs || !qt || !res) return -1;
-  return conv2d_impl(x, w, y, res, nullptr, nullptr, nullptr, N, H, W, C, Cout, 1, stride, 0, 0, nullptr, nullptr,
-                     nullptr, 0, 1, s, static_cast<float*>(ws), ws_bytes, nullptr, nullptr, nullptr, nullptr, 0, qs,
-                     qt);
+  ConvArgs a = conv_args(x, w, y, res, N, H, W, C, Cout, stride, 0);
+  a.qscale = qs; a.qshift = qt;
+  a.ws = static_cast<float*>(ws);
+  return conv2d_impl(a, 1, ws_bytes, s);
 }
 
 VGPU_API void vgpu_conv_set_splitk(int mode) { g_forced_split = mode; }
@@ -2813,15 +2786,9 @@ VGPU_API void vgpu_conv_set_splitk(int mode) { g_forced_split = mode; }
 VGPU_API int vgpu_conv2d_masked_splitk(const void* x, const void* w, void* y, int N, int H, int W, int C, int Cout,
                                        int KS, int pad, const void* gmask, void* gpart, int64_t gpart_bytes,
                                        void* ws, int64_t ws_bytes, int* blocks_out, hipStream_t s) {
-  if (!gmask || !gpart || !ws || Cout % 8 || kThreads % (Cout / 8) || KS < 1 || pad < 0) return -1;
-  const int64_t OH = H + 2 * pad - KS + 1, OW = W + 2 * pad - KS + 1;
-  if (OH < 1 || OW < 1) return -1;
-  const int64_t M = (int64_t)N * OH * OW;
-  const int64_t blocks = (M * (Cout / 8) + kThreads - 1) / kThreads;
-  if (vgpu_conv2d_workspace(N, H, W, C, Cout, KS, 1, pad, 0) <= 0 || gpart_bytes < blocks * Cout * 4) return -1;
-  if (blocks_out) *blocks_out = (int)blocks;
-  return conv2d_impl(x, w, y, nullptr, nullptr, nullptr, nullptr, N, H, W, C, Cout, KS, 1, pad, 0, nullptr, nullptr,
-                     nullptr, 0, 1, s, static_cast<float*>(ws), ws_bytes, gmask, static_cast<float*>(gpart));
+  ConvArgs a = conv_args(x, w, y, nullptr, N, H, W, C, Cout, 1, pad);
+  if (!masked_args(a, KS, gmask, gpart, gpart_bytes, ws, blocks_out)) return -1;
+  return conv2d_impl(a, KS, ws_bytes, s);
 }
 
 // The same for a ReLU layer followed by a k×k / stride-k max pool whose output
@@ -2835,14 +2802,11 @@ VGPU_API int vgpu_conv2d_masked_pool_splitk(const void* x, const void* w, int N,
   if (!pidx || !gfull || pk < 1 || pk > 15) return -1;
   const int64_t OH = H + 2 * pad - KS + 1, OW = W + 2 * pad - KS + 1;
   if (OH < 1 || OW < 1 || (int64_t)N * OH * pk * OW * pk * Cout * 2 >= ((int64_t)1 << 31)) return -1;
-  if (!gmask || !gpart || !ws || Cout % 8 || kThreads % (Cout / 8) || KS < 1 || pad < 0) return -1;
-  const int64_t M = (int64_t)N * OH * OW;
-  const int64_t blocks = (M * (Cout / 8) + kThreads - 1) / kThreads;
-  if (vgpu_conv2d_workspace(N, H, W, C, Cout, KS, 1, pad, 0) <= 0 || gpart_bytes < blocks * Cout * 4) return -1;
-  if (blocks_out) *blocks_out = (int)blocks;
-  return conv2d_impl(x, w, nullptr, nullptr, nullptr, nullptr, nullptr, N, H, W, C, Cout, KS, 1, pad, 0, nullptr,
-                     nullptr, nullptr, 0, 1, s, static_cast<float*>(ws), ws_bytes, gmask, static_cast<float*>(gpart),
-                     pidx, gfull, pk);
+  ConvArgs a = conv_args(x, w, nullptr, nullptr, N, H, W, C, Cout, 1, pad);
+  if (!masked_args(a, KS, gmask, gpart, gpart_bytes, ws, blocks_out)) return -1;
+  a.pidx = static_cast<const uint8_t*>(pidx);
+  a.gfull = static_cast<uint16_t*>(gfull); a.pk = pk;
+  return conv2d_impl(a, KS, ws_bytes, s);
 }
 
 // Training convolution with the BatchNorm statistics of its output from the
@@ -2862,176 +2826,13 @@ VGPU_API int vgpu_conv2d_nhwc_bn(const void* x, const void* w, void* y, const vo
                                  const float* bncoef, int bnact, int res_stride, hipStream_t s) {
   if (!stats || (bnx && !bncoef) || bnact < 0 || bnact > 2 || (res_stride != 1 && (res_stride != 2 || !bnx || !res)))
     return -1;
-  return conv2d_impl(x, w, y, res, nullptr, nullptr, nullptr, N, H, W, C, Cout, KS, stride, pad, 0, stats, bnx,
-                     bncoef, bnact, res_stride, s);
-}
-
-namespace {
-int conv2d_impl(const void* x, const void* w, void* y, const void* res, const float* bias, const float* pscale,
-                const float* pshift, int N, int H, int W, int C, int Cout, int KS, int stride, int pad, int act,
-                float* stats, const void* bnx, const float* bncoef, int bnact, int res_stride, hipStream_t s,
-                float* ws, int64_t ws_bytes, const void* gmask, float* gpart, const void* pidx, void* gfull,
-                int pk, const float* qscale, const float* qshift) {
-  const int bias_bf16 = (act >> 8) & 1;
-  act &= 0xff;
-  if (act > 2) return -1;
-  // C % 64 == 0 with 1x1 / 3x3 filters, or the narrow stem form (C = 16, 4x4,
-  // stride 1, no prologue: a 7x7/s2 conv on a space-to-depth input).
-  const bool narrow = C == 16 && KS == 4 && stride == 1 && pscale == nullptr;
-  if (!narrow && (C % 64 || (KS != 1 && KS != 3))) return -1;
-  if (Cout % 64 || stride < 1 || pad < 0 || N < 1) return -1;
-  if ((pscale == nullptr) != (pshift == nullptr)) return -1;
-  ConvArgs a{};
-  a.x = static_cast<const uint16_t*>(x);
-  a.w = static_cast<const uint16_t*>(w);
-  a.y = static_cast<uint16_t*>(y);
-  a.res = static_cast<const uint16_t*>(res);
-  a.bias = bias;
-  a.pscale = pscale;
-  a.pshift = pshift;
-  a.N = N; a.H = H; a.W = W; a.C = C; a.Cout = Cout; a.stride = stride; a.pad = pad;
-  a.OH = (H + 2 * pad - KS) / stride + 1;
-  a.OW = (W + 2 * pad - KS) / stride + 1;
-  if (a.OH < 1 || a.OW < 1) return -1;
-  a.K = KS * KS * C;
-  a.cblocks = C / 64;
-  a.ktiles = a.K / 64;
-  a.act = act;  // 0 none, 1 ReLU, 2 ReLU6
-  a.bias_bf16 = bias_bf16;
+  ConvArgs a = conv_args(x, w, y, res, N, H, W, C, Cout, stride, pad);
   a.stats = reinterpret_cast<float2*>(stats);
   a.bnx = static_cast<const uint16_t*>(bnx);
-  a.bncoef = bncoef;
-  a.bnact = bnact;
-  a.res_stride = res_stride;
-  a.res_h = (a.OH + 1) / 2;
-  a.res_w = (a.OW + 1) / 2;
-  a.res_bytes = 0;
-  if (res_stride == 2) {
-    const int64_t rb = (int64_t)N * a.res_h * a.res_w * Cout * 2;
-    if (rb >= ((int64_t)1 << 31)) return -1;
-    a.res_bytes = (uint32_t)rb;
-  }
-  const bool pro = pscale != nullptr, has_res = res != nullptr;
-  if (stats && (narrow || pro)) return -1;
-  // Post epilogue: the 1x1 + residual LDS-DMA kernels (and their split-K reduce) only.
-  const bool post = qscale != nullptr;
-  if ((qscale == nullptr) != (qshift == nullptr)) return -1;
-  if (post && (KS != 1 || pro || !has_res || stats || gmask || act != 0 || bias)) return -1;
-  a.qscale = qscale;
-  a.qshift = qshift;
-  // Buffer offsets are 32-bit: run the batch in slices whose activations stay < 2 GiB.
-  const int64_t xi = (int64_t)H * W * C * 2, yi = (int64_t)a.OH * a.OW * Cout * 2;
-  const int64_t lim = ((int64_t)1 << 31) - 1;
-  const int64_t per = lim / (xi > yi ? xi : yi);
-  if (per < 1 || (stats && per < N)) return -1;  // statistics: one slice (group rows are global)
-  if (post && per < N) return -1;  // one slice, so -1 comes before any launch
-  const int bn = (Cout % 128 == 0) ? 128 : 64;
-  for (int n0 = 0; n0 < N; n0 += (int)per) {
-    const int nb = (int)((N - n0) < per ? (N - n0) : per);
-    ConvArgs c = a;
-    c.N = nb;
-    c.x = a.x + (int64_t)n0 * (xi / 2);
-    c.y = a.y + (int64_t)n0 * (yi / 2);
-    if (has_res) c.res = a.res + (int64_t)n0 * (yi / 2);
-    c.x_bytes = (uint32_t)(nb * xi);
-    c.y_bytes = (uint32_t)(nb * yi);
-    c.M = nb * a.OH * a.OW;
-    // Small-M layers use 64-row tiles so the grid still fills the CUs this
-    // process owns: 128-row tiles fetch fewer bytes per FLOP, but below ~1.5
-    // workgroups per CU the kernel is latency-bound (profiles/conv_cus_r1.md:
-    // exclusive 256 CUs and 50 % pods of 128 CUs agree with this threshold).
-    const int64_t tiles128 = (int64_t)((c.M + 127) / 128) * (Cout / bn);
-    bool small = tiles128 < (int64_t)conv_cus() * 3 / 2;
-    // Non-prologue 1x1 convs (conv3 + residual) are DMA/HBM-bound: 64-row tiles
-    // (48 KB LDS → 3 blocks per CU) beat 128-row tiles on every ResNet-50 shape
-    // (profiles/conv_tiles_r1.md).  Without a residual, from K = 256 and 128
-    // outputs up -- a projection block's shortcut and conv1 on a pre-activated
-    // input -- 128-row tiles measured 2-7 % ahead on all six such flagship
-    // shapes (profiles/r7/preact), so those keep the grid-fill rule above;
-    // K = 64 (block 0) stays on 64-row tiles (tie / 6 % behind).
-    const bool rows128_ok = !has_res && !stats && C >= 256 && Cout >= 128;
-    if (!pro && KS == 1 && !rows128_ok) small = !conv_1x1_big();
-    if (g_forced_bm == 64) small = true;
-    if (g_forced_bm == 128) small = false;
-    hipError_t e;
-    int kper;
-    const int splits = (ws && !stats && per >= N) ? splitk_plan(c.M, C, Cout, KS, pro, narrow, kper) : 1;
-    if (gmask && splits <= 1) return -1;  // the masked form exists only as a split-K reduce
-    if (splits > 1) {
-      if (ws_bytes < (int64_t)splits * c.M * Cout * 4) return -1;
-      c.ws = ws;
-      c.kper = kper;
-      c.splits = splits;
-      c.gmask = static_cast<const uint16_t*>(gmask);
-      c.gpart = gpart;
-      c.pidx = static_cast<const uint8_t*>(pidx);
-      c.gfull = static_cast<uint16_t*>(gfull);
-      c.pk = pk;
-      c.nM = (c.M + 63) / 64;
-      c.nN = Cout / bn;
-      c.nwg = c.nM * c.nN;
-      const dim3 grid(c.nwg, splits);
-      if (bn == 128) {
-        if (KS == 1) hipLaunchKernelGGL((conv_glds_kernel<1, 64, 128, false, 0, 0, true>), grid, dim3(kThreads), 0, s, c);
-        else hipLaunchKernelGGL((conv_glds_kernel<3, 64, 128, false, 0, 0, true>), grid, dim3(kThreads), 0, s, c);
-      } else {
-        if (KS == 1) hipLaunchKernelGGL((conv_glds_kernel<1, 64, 64, false, 0, 0, true>), grid, dim3(kThreads), 0, s, c);
-        else hipLaunchKernelGGL((conv_glds_kernel<3, 64, 64, false, 0, 0, true>), grid, dim3(kThreads), 0, s, c);
-      }
-      if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-      const int64_t threads = (int64_t)c.M * (Cout / 8);
-      hipLaunchKernelGGL(post ? splitk_reduce_kernel<true> : splitk_reduce_kernel<false>,
-                         dim3((unsigned)((threads + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, c);
-      if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-      continue;
-    }
-    // LDS-DMA kernels for every conv without a prologue; prologue convs stage A
-    // through registers (conv_pro_kernel / conv_gemm_kernel).
-    const bool glds = !pro;
-    // 256x256 tiles: 1x1 / stride 1 / no prologue, Cout % 256 == 0, deep K
-    // (≥ 1024: below it these layers are HBM-bound and the 64-row tiles at 3
-    // blocks per CU win — the ResNet-50 flagship measured 1 % slower with the
-    // big tile on its K = 128-512 conv3 layers), and enough tiles to give every
-    // CU this process owns at least one.
-    if (g_forced_big < 0) {
-      const char* v = getenv("VGPU_CONV_BIG");
-      g_forced_big = v ? (v[0] == '1' ? 1 : (v[0] == '0' ? 0 : 2)) : 2;
-    }
-    const bool big_ok = !narrow && !pro && KS == 1 && stride == 1 && pad == 0 && Cout % 256 == 0 && C >= 128;
-    const int64_t tiles256 = (int64_t)((c.M + 255) / 256) * (Cout / 256);
-    const bool big = !stats && big_ok && (g_forced_big == 1 ||
-                                (g_forced_big == 2 && C >= 1024 && tiles256 >= (int64_t)conv_cus()));
-    // 3x3 / stride 1 without prologue or residual: the halo-tile kernel.
-    const bool halo = (g_forced_halo < 0 ? halo_enabled() : g_forced_halo > 0) && !narrow && !pro && !has_res &&
-                      KS == 3 && stride == 1 && pad == 1;
-    if (post) {
-      if (big) return -1;  // the 256x256 tile has no post epilogue (first launch of the only slice)
-      e = small ? dispatch_glds_post<64>(c, s) : dispatch_glds_post<128>(c, s);
-    } else if (halo && (e = dispatch_halo(c, s)) != hipErrorNotSupported) {
-      // launched (or a launch error)
-    } else if (big)
-      e = has_res ? launch_big<true>(c, s) : launch_big<false>(c, s);
-    else if (narrow)
-      e = small ? launch_glds<4, 64, 64, false, 16>(c, s) : launch_glds<4, 128, 64, false, 16>(c, s);
-    // Short K (≤ 2 steps) or 64-wide outputs: the persistent register kernel,
-    // which overlaps the next tile's loads with this tile's epilogue, wins there.
-    // (conv_pro's 1x1 form assumes no padding: it skips the zero-padding select.)
-    else if (pro && C <= 2048 && a.ktiles > 2 && Cout > 64 && (KS != 1 || pad == 0))
-      e = KS == 1 ? (small ? dispatch_pro<1, 64>(c, has_res, s) : dispatch_pro<1, 128>(c, has_res, s))
-                  : (small ? dispatch_pro<3, 64>(c, has_res, s) : dispatch_pro<3, 128>(c, has_res, s));
-    else if (glds)
-      e = KS == 1 ? (small ? dispatch_glds<1, 64>(c, has_res, s) : dispatch_glds<1, 128>(c, has_res, s))
-                  : (small ? dispatch_glds<3, 64>(c, has_res, s) : dispatch_glds<3, 128>(c, has_res, s));
-    else if (KS == 1)
-      e = small ? dispatch_bn<1, 64>(c, pro, has_res, s) : dispatch_bn<1, 128>(c, pro, has_res, s);
-    else
-      e = small ? dispatch_bn<3, 64>(c, pro, has_res, s) : dispatch_bn<3, 128>(c, pro, has_res, s);
-    if (e == hipErrorNotSupported && stats) return -1;
-    if (e != hipSuccess) return (int)e;
-  }
-  return 0;
+  a.bncoef = bncoef; a.bnact = bnact; a.res_stride = res_stride;
+  return conv2d_impl(a, KS, 0, s);
 }
-}  // namespace
+
 
 // NHWC bf16 max pool (k×k window, stride, symmetric zero-excluded padding), 16 B per lane.
 // Fused stem: X [N][HS][WS][16] (space-to-depth input), w [64][4][4][16] →
@@ -3047,11 +2848,7 @@ static int stem_pool_impl(const void* X, const void* w, void* y, const float* qs
   // One workgroup per CU of the device (LDS allows one), not conv_cus(): a
   // time-shared pod runs on every CU while it runs, and a masked one just
   // queues the extra workgroups (the task loop takes any grid).
-  int dev = 0, grid = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&grid, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || grid < 1)
-    grid = 256;
-  if (grid > tasks) grid = tasks;
+  const int grid = device_cus() < tasks ? device_cus() : tasks;
   hipLaunchKernelGGL(qs ? stem_pool_kernel<true> : stem_pool_kernel<false>, dim3(grid), dim3(kSPThreads), 0, s,
                      static_cast<const uint16_t*>(X), static_cast<const uint16_t*>(w), static_cast<uint16_t*>(y), HS,
                      WS, OH, OW, PH, PW, tasks, qs, qt);

@@ -23,12 +23,14 @@ LDS_PER_CU = 160 * 1024
 
 
 def demangle(names: list[str]) -> dict[str, str]:
-    try:
-        out = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-cxxfilt"], input="\n".join(names), capture_output=True,
-                             text=True, check=True).stdout.splitlines()
-        return dict(zip(names, out))
-    except (OSError, subprocess.CalledProcessError):
-        return {n: n for n in names}
+    for tool in ("/opt/rocm/lib/llvm/bin/llvm-cxxfilt", "c++filt"):  # ROCm's, else binutils'
+        try:
+            out = subprocess.run([tool], input="\n".join(names), capture_output=True, text=True,
+                                 check=True).stdout.splitlines()
+            return dict(zip(names, out))
+        except (OSError, subprocess.CalledProcessError):
+            continue
+    return {n: n for n in names}
 
 
 def resources(src: Path) -> list[dict]:
