@@ -38,6 +38,7 @@
 #include <string.h>
 
 #include "conv_plan.h"
+#include "stem_plan.h"
 
 #define VGPU_API extern "C" __attribute__((visibility("default")))
 
@@ -2144,6 +2145,7 @@ int g_forced_big = -1;    // vgpu_conv_set_big: -1 = env VGPU_CONV_BIG / heurist
 int g_forced_halo = -1;   // vgpu_conv_set_halo: -1 = env VGPU_CONV_HALO, 0 = off, 1 = on, 2 / 3 = on with BM 256 / 128
 int g_forced_split = -1;  // vgpu_conv_set_splitk: -1 heuristic, 0 off, n > 1 that many splits when eligible
 unsigned long long g_halo_launches = 0;  // vgpu_conv_halo_launches (tests: the halo path ran)
+int g_stem_band = 0;      // vgpu_stem_set_band: 0 = stem_plan.h's rule, k = bands of k pooled rows
 
 convplan::ConvKnobs conv_knobs() {
   const char* big = g_forced_big < 0 ? getenv("VGPU_CONV_BIG") : nullptr;
@@ -2358,44 +2360,237 @@ __global__ void __launch_bounds__(kThreads) s2d_stem_kernel(const uint16_t* __re
 // ---- ResNet stem conv + 3x3/s2 max pool in one persistent kernel ----------
 // The stem conv (4x4/s1 over the space-to-depth input, C = 16, 64 outputs)
 // writes a 4x-wide activation (b=50 at 346²: 191 MB) that the max pool reads
-// straight back.  Here one task = one pooled output row (n, i): the stem rows
-// 2i-1 .. 2i+1 are computed from a 6-row input slab in LDS and rounded to bf16
-// into LDS row buffers (exactly what the unfused conv stores), then
-// max-pooled from there, so only the input slab and the pooled row touch HBM.
-// The 32 KB filter is loaded once per workgroup; the next task's slab is
-// fetched into registers while the current task computes.
-// The three stem rows are 3 x 11 pixel subtiles of 16; subtile s goes to wave
-// s % 8, which computes all 64 channels of it (4 B fragments shared by up to 5
-// A fragments per K step).  mfma(B, A) (transposed tile) so a lane holds 4
+// straight back.  Here a workgroup walks a band: the pooled rows [p0, p1) of
+// one image (stem_plan.h has the band rule).  One step = one pooled row pi.  The
+// band's first step computes the stem rows 2pi-1 .. 2pi+1, every later step
+// only 2pi and 2pi+1: the rows are rounded to bf16 into three LDS row buffers
+// (exactly what the unfused conv stores; stem row s lives in buffer s mod 3,
+// so row 2pi-1 is still there from the step before) and max-pooled from there.
+// The space-to-depth input is a ring of six rows in LDS (row r in slot r mod
+// 6): a stem row s reads input rows s .. s+3, so a step needs 2pi .. 2pi+4 (a
+// first step 2pi-1 too) and the next one only the two new rows 2pi+5, 2pi+6,
+// which replace two rows no later step reads.  So only the input and the
+// pooled row touch HBM, and per step two input rows instead of six.
+// The 32 KB filter is loaded once per workgroup.  The next step's two rows (or
+// the six of the workgroup's next band) are fetched into registers at the
+// start of a step, raw and unmasked so that nothing waits for them before the
+// MFMAs, and go to the ring after the step's first barrier, ahead of the pool.
+// Two barriers per step: one between the stem-row stores and the pool (it
+// also ends the step's ring reads), one after the ring stores and the pool.
+// DIRECT: the ring is filled from the image x [N][H][W][3] itself, by
+// s2d_stem_kernel's own rule per pixel (a 2-byte-aligned dword and a 2-byte
+// load per tap: x is only 2-byte aligned when W is odd), so the space-to-depth
+// tensor never exists.  Two new rows are at most one pixel per thread and the
+// gather hides behind the MFMAs (profiles/r10/stem), so the alternative --
+// raw image rows staged with wide loads and permuted LDS → LDS -- was not built.
+// Otherwise `in` is that tensor, X [N][HS][WS][16].
+// The ROWS x 11 pixel subtiles of 16 of a step go to wave s % 8, which computes
+// all 64 channels of a subtile (4 B fragments shared by up to 5 A fragments per
+// K step): 22 subtiles are 3/3/3/3/3/3/2/2, which is 6/6/5/5 on the four SIMDs
+// where 5.5 is even (no other deal was measured; splitting remainder subtiles
+// by channel block was slower once, docs/benchmarks.md).  mfma(B, A) (transposed tile) so a lane holds 4
 // consecutive channels of one pixel.  K order (kh, kw, c) and the MFMA
 // sequence match the unfused stem conv, so the result is bit-identical to
-// conv + maxpool (tests/test_gpu_conv.py).
+// conv + maxpool (tests/test_gpu_conv.py, tests/test_gpu_stem_direct.py).
 // POST: the pooled row goes out through the post epilogue, relu(y·qs[c] + qt[c])
 // (the entry BN+ReLU of the first block, whose two convs are its only readers).
 constexpr int kSPThreads = 512;
 constexpr int kSPMaxOW = 176;   // 11 pixel subtiles of 16
-constexpr int kSPMaxWS = 180;
+constexpr int kSPMaxWS = 180;   // ring row pitch in pixels: the last subtile's taps end at pixel 178
+constexpr int kSPRowBuf = kSPMaxOW * 128;  // one bf16 stem row [pixel][64 ch] swizzled
+constexpr int kSPRingRow = kSPMaxWS * 32;  // one input row [px][16 ch]
+constexpr int kSPXR = 24;       // fetch registers: 3 pixels x 4 x (dword + ushort) (DIRECT), 5 chunks x 4 dwords (X)
 
+// Input rows [row0, row0 + nrows), nrows <= 6, of image n → registers, nothing
+// waited for: a load outside the input reads element 0 instead and `mask`
+// says which values stem_ring_store() zeroes.
+template <bool DIRECT>
+__device__ __forceinline__ void stem_fetch(const uint16_t* __restrict__ in, int n, int row0, int nrows, int H, int W,
+                                           int HS, int WS, int t, uint32_t (&xr)[kSPXR], uint32_t& mask) {
+  mask = 0;
+  if constexpr (DIRECT) {
+    // thread = one input pixel (i, j): x rows 2i+b-3, columns 2j+b'-3, 3 channels each
+    const uint16_t* __restrict__ xn = in + (int64_t)n * H * W * 3;
+    const int cnt = nrows * WS;
+#pragma unroll
+    for (int u = 0; u < 3; ++u) {
+      const int k = t + kSPThreads * u;
+      if (k < cnt) {
+        const int q = (int)((unsigned)k / (unsigned)WS), j = k - q * WS, i = row0 + q;
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+          const int r = 2 * i + b - 3;
+#pragma unroll
+          for (int b2 = 0; b2 < 2; ++b2) {
+            const int c0 = 2 * j + b2 - 3;
+            const bool ok = (unsigned)r < (unsigned)H && (unsigned)c0 < (unsigned)W;
+            const uint16_t* src = xn + (ok ? (r * W + c0) * 3 : 0);
+            // channels 0, 1 as one 2-byte-aligned dword, channel 2 zero-extended: kept as loaded
+            __builtin_memcpy(&xr[u * 8 + b * 4 + b2 * 2], src, 4);
+            xr[u * 8 + b * 4 + b2 * 2 + 1] = src[2];
+            mask |= (uint32_t)ok << (u * 4 + b * 2 + b2);
+          }
+        }
+      }
+    }
+  } else {
+    // thread = 16-B chunks of X rows
+    const int rowc = WS * 2, cnt = nrows * rowc;
+#pragma unroll
+    for (int u = 0; u < 5; ++u) {
+      const int k = t + kSPThreads * u;
+      if (k < cnt) {
+        const int q = (int)((unsigned)k / (unsigned)rowc), rem = k - q * rowc, row = row0 + q;
+        const bool ok = (unsigned)row < (unsigned)HS;
+        const u32x4 v = *reinterpret_cast<const u32x4*>(in + ((int64_t)(n * HS + (ok ? row : 0)) * WS) * 16 + rem * 8);
+        xr[u * 4] = v.x; xr[u * 4 + 1] = v.y; xr[u * 4 + 2] = v.z; xr[u * 4 + 3] = v.w;
+        mask |= (uint32_t)ok << u;
+      }
+    }
+  }
+}
+
+// What stem_fetch() fetched → the ring (input row r in slot (r + 6) % 6; row0 >= -1).
+template <bool DIRECT>
+__device__ __forceinline__ void stem_ring_store(char* sX, int row0, int nrows, int WS, int t,
+                                                const uint32_t (&xr)[kSPXR], uint32_t mask) {
+  if constexpr (DIRECT) {
+    const int cnt = nrows * WS;
+#pragma unroll
+    for (int u = 0; u < 3; ++u) {
+      const int k = t + kSPThreads * u;
+      if (k < cnt) {
+        const int q = (int)((unsigned)k / (unsigned)WS), j = k - q * WS, slot = (row0 + q + 6) % 6;
+        uint32_t lo[4], hi[4];  // per (b, b'): channels 0, 1 and channel 2
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const bool ok = (mask >> (u * 4 + e)) & 1u;
+          lo[e] = ok ? xr[u * 8 + e * 2] : 0u;
+          hi[e] = ok ? xr[u * 8 + e * 2 + 1] : 0u;
+        }
+        u32x4* dst = reinterpret_cast<u32x4*>(sX + slot * kSPRingRow + j * 32);
+        dst[0] = u32x4{lo[0], hi[0] | (lo[1] << 16), (lo[1] >> 16) | (hi[1] << 16), lo[2]};
+        dst[1] = u32x4{hi[2] | (lo[3] << 16), (lo[3] >> 16) | (hi[3] << 16), 0u, 0u};
+      }
+    }
+  } else {
+    const int rowc = WS * 2, cnt = nrows * rowc;
+#pragma unroll
+    for (int u = 0; u < 5; ++u) {
+      const int k = t + kSPThreads * u;
+      if (k < cnt) {
+        const int q = (int)((unsigned)k / (unsigned)rowc), rem = k - q * rowc, slot = (row0 + q + 6) % 6;
+        const bool ok = (mask >> u) & 1u;
+        *reinterpret_cast<u32x4*>(sX + slot * kSPRingRow + rem * 16) =
+            ok ? u32x4{xr[u * 4], xr[u * 4 + 1], xr[u * 4 + 2], xr[u * 4 + 3]} : u32x4{0u, 0u, 0u, 0u};
+      }
+    }
+  }
+}
+
+// The stem rows sr0 .. sr0 + ROWS - 1 (sr0 >= -1) from the ring → bf16 into their
+// row buffers.  This wave's subtiles are s = wave + 8u: row s / MT, pixels (s % MT)*16 ..
+template <int ROWS>
+__device__ __forceinline__ void stem_rows(const char* sW, const char* sX, char* sR, int sr0, int MT, int wave, int fr,
+                                          int fk) {
+  constexpr int NS = (ROWS * (kSPMaxOW / 16) + 7) / 8;  // subtiles per wave
+  f32x4_t acc[NS][4];
+  int rl[NS], m[NS], xs[NS];
+#pragma unroll
+  for (int u = 0; u < NS; ++u) {
+    const int sidx = wave + 8 * u;
+    rl[u] = sidx / MT;
+    m[u] = sidx - rl[u] * MT;
+    xs[u] = (sr0 + rl[u] + 6) % 6;  // ring slot of the subtile's tap row kh = 0
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[u][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  }
+#pragma unroll
+  for (int kh = 0; kh < 4; ++kh)
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      bf16x8_t bfr[4], af[NS];
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        bfr[j] = *reinterpret_cast<const bf16x8_t*>(sW + kh * 8192 + swz(j * 16 + fr, kk * 4 + fk));
+#pragma unroll
+      for (int u = 0; u < NS; ++u) {
+        const int slot = xs[u] + kh < 6 ? xs[u] + kh : xs[u] + kh - 6;
+        if (rl[u] < ROWS)  // wave-uniform; past the step's rows there is nothing to read
+          af[u] = *reinterpret_cast<const bf16x8_t*>(sX + slot * kSPRingRow + (m[u] * 16 + fr) * 32 +
+                                                     (kk * 4 + fk) * 16);
+      }
+#pragma unroll
+      for (int u = 0; u < NS; ++u)
+        if (rl[u] < ROWS)
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            acc[u][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[u], acc[u][j], 0, 0, 0);
+    }
+  // bf16 stem rows → LDS: lane holds pixel m*16+fr, channels j*16+fk*4 .. +3
+#pragma unroll
+  for (int u = 0; u < NS; ++u) {
+    if (rl[u] >= ROWS) continue;
+    const int p = m[u] * 16 + fr;
+    char* row = sR + ((sr0 + rl[u] + 3) % 3) * kSPRowBuf + p * 128;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int slot = j * 2 + (fk >> 1);
+      *reinterpret_cast<uint2*>(row + ((slot ^ (p & 7)) << 4) + (fk & 1) * 8) =
+          uint2{pack2(acc[u][j][0], acc[u][j][1]), pack2(acc[u][j][2], acc[u][j][3])};
+    }
+  }
+}
+
+// 3x3/s2 window of pooled row pi from the row buffers (the stem rows 2pi-1 .. 2pi+1
+// that exist, columns 2j-1 .. 2j+1) → y, through the post epilogue if POST.
 template <bool POST>
-__global__ void __launch_bounds__(kSPThreads, 1) stem_pool_kernel(const uint16_t* __restrict__ X,
+__device__ __forceinline__ void stem_pool_row(const char* sR, uint16_t* __restrict__ y, int n, int pi, int OH, int OW,
+                                              int PH, int PW, int t, const float (&psc)[8], const float (&psh)[8]) {
+  const int r0 = 2 * pi - 1;
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int it = t + kSPThreads * k, j = it >> 3, q = it & 7;
+    if (j >= PW) continue;
+    float pm[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) pm[e] = -INFINITY;
+#pragma unroll
+    for (int rl = 0; rl < 3; ++rl) {
+      if (r0 + rl < 0 || r0 + rl >= OH) continue;
+      const char* row = sR + ((r0 + rl + 3) % 3) * kSPRowBuf;
+#pragma unroll
+      for (int dc = -1; dc <= 1; ++dc) {
+        const int c = 2 * j + dc;
+        if (c < 0 || c >= OW) continue;
+        float e[8];
+        unpack8(*reinterpret_cast<const u32x4*>(row + c * 128 + ((q ^ (c & 7)) << 4)), e);
+#pragma unroll
+        for (int u = 0; u < 8; ++u) pm[u] = fmaxf(pm[u], e[u]);
+      }
+    }
+    u32x4 o = pack8(pm);  // exact: pm are bf16 values
+    if constexpr (POST) o = post_act8(o, psc, psh);
+    *reinterpret_cast<u32x4*>(y + ((int64_t)(n * PH + pi) * PW + j) * 64 + q * 8) = o;
+  }
+}
+
+template <bool POST, bool DIRECT>
+__global__ void __launch_bounds__(kSPThreads, 1) stem_pool_kernel(const uint16_t* __restrict__ in,
                                                                   const uint16_t* __restrict__ w,
-                                                                  uint16_t* __restrict__ y, int HS, int WS,
-                                                                  int OH, int OW, int PH, int PW, int tasks,
+                                                                  uint16_t* __restrict__ y, int H, int W, int HS,
+                                                                  int WS, int OH, int OW, int PH, int PW,
+                                                                  stemplan::StemPlan plan,
                                                                   const float* __restrict__ qs,
                                                                   const float* __restrict__ qt) {
-  constexpr int SW_BYTES = 4 * 64 * 128;         // [kh][cout][128 B] swizzled
-  constexpr int SR_BYTES = 3 * kSPMaxOW * 128;   // three bf16 stem rows [row][pixel][64 ch] swizzled
-  constexpr int SX_BYTES = 6 * kSPMaxWS * 32 + 512;  // 6 input rows [px][16 ch] + over-read pad
-  constexpr int XR = (6 * kSPMaxWS * 2 + kSPThreads - 1) / kSPThreads;  // slab chunks per thread
-  constexpr int NS = 5;                          // subtiles per wave (33 over 8 waves)
-  __shared__ __attribute__((aligned(16))) char smem[SW_BYTES + SR_BYTES + SX_BYTES];
+  constexpr int SW_BYTES = 4 * 64 * 128;  // [kh][cout][128 B] swizzled
+  __shared__ __attribute__((aligned(16))) char smem[SW_BYTES + 3 * kSPRowBuf + 6 * kSPRingRow];
   char* sW = smem;
   char* sR = smem + SW_BYTES;
-  char* sX = sR + SR_BYTES;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  char* sX = sR + 3 * kSPRowBuf;
+  const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int fr = lane & 15, fk = lane >> 4;
   const int MT = (OW + 15) >> 4;
-  const int rowc = WS * 2, nchunk = 6 * rowc;  // 16-B chunks per slab row / per slab
 
   // filter → LDS once: chunk k = (cout, kh, slot)
 #pragma unroll
@@ -2404,113 +2599,57 @@ __global__ void __launch_bounds__(kSPThreads, 1) stem_pool_kernel(const uint16_t
     *reinterpret_cast<u32x4*>(sW + (c16 >> 3) * 8192 + swz(co, c16 & 7)) =
         *reinterpret_cast<const u32x4*>(w + co * 256 + c16 * 8);
   }
-  auto load_slab = [&](int task, u32x4 (&xr)[XR]) {
-    const int n = task / PH, r0 = 2 * (task - n * PH) - 1;
-#pragma unroll
-    for (int u = 0; u < XR; ++u) {
-      const int k = t + kSPThreads * u, q = k / rowc, rem = k - q * rowc, row = r0 + q;
-      const bool ok = k < nchunk && row >= 0 && row < HS;
-      xr[u] = ok ? *reinterpret_cast<const u32x4*>(X + ((int64_t)(n * HS + row) * WS) * 16 + rem * 8)
-                 : u32x4{0u, 0u, 0u, 0u};
-    }
-  };
-  auto store_slab = [&](const u32x4 (&xr)[XR]) {
-#pragma unroll
-    for (int u = 0; u < XR; ++u) {
-      const int k = t + kSPThreads * u;
-      if (k < nchunk) *reinterpret_cast<u32x4*>(sX + k * 16) = xr[u];
-    }
-  };
   // post parameters of this thread's 8 pooled channels (q = t & 7 in the window loop)
   float psc[8], psh[8];
   if constexpr (POST) {
     load8f(qs + (t & 7) * 8, psc);
     load8f(qt + (t & 7) * 8, psh);
   }
-  u32x4 xr[XR];
-  int task = blockIdx.x;
-  if (task < tasks) {
-    load_slab(task, xr);
-    store_slab(xr);
+  int b = blockIdx.x;
+  if (b >= plan.nbands) return;
+  stemplan::StemBand band = stemplan::stem_band(plan, PH, b);
+  int pi = band.p0;
+  {
+    uint32_t xr[kSPXR], xmask;
+    stem_fetch<DIRECT>(in, band.n, 2 * pi - 1, 6, H, W, HS, WS, t, xr, xmask);
+    stem_ring_store<DIRECT>(sX, 2 * pi - 1, 6, WS, t, xr, xmask);
   }
+  __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the loop is entered with no load pending
   __syncthreads();
-  for (; task < tasks; task += gridDim.x) {
-    const int n = task / PH, pi = task - n * PH, r0 = 2 * pi - 1;
-    const int next = task + gridDim.x;
-    if (next < tasks) load_slab(next, xr);  // lands behind this task's compute
-    // this wave's subtiles s = wave + 8u: stem row rl = s / MT, pixels (s % MT)*16 ..
-    f32x4_t acc[NS][4];
-#pragma unroll
-    for (int u = 0; u < NS; ++u)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[u][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kh = 0; kh < 4; ++kh)
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        bf16x8_t bfr[4], af[NS];
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          bfr[j] = *reinterpret_cast<const bf16x8_t*>(sW + kh * 8192 + swz(j * 16 + fr, kk * 4 + fk));
-#pragma unroll
-        for (int u = 0; u < NS; ++u) {
-          const int sidx = wave + 8 * u, rl = sidx / MT, m = sidx - rl * MT;
-          if (sidx < 3 * MT)  // wave-uniform; past the three rows there is nothing to read
-            af[u] = *reinterpret_cast<const bf16x8_t*>(
-                sX + (((rl + kh) * WS + m * 16 + fr) * 32) + (kk * 4 + fk) * 16);
-        }
-#pragma unroll
-        for (int u = 0; u < NS; ++u)
-          if (wave + 8 * u < 3 * MT)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-              acc[u][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[u], acc[u][j], 0, 0, 0);
-      }
-    // bf16 stem rows → LDS: lane holds pixel m*16+fr, channels j*16+fk*4 .. +3
-#pragma unroll
-    for (int u = 0; u < NS; ++u) {
-      const int sidx = wave + 8 * u, rl = sidx / MT, m = sidx - rl * MT;
-      if (rl >= 3) continue;
-      const int p = m * 16 + fr;
-      char* row = sR + rl * (kSPMaxOW * 128) + p * 128;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int slot = j * 2 + (fk >> 1);
-        *reinterpret_cast<uint2*>(row + ((slot ^ (p & 7)) << 4) + (fk & 1) * 8) =
-            uint2{pack2(acc[u][j][0], acc[u][j][1]), pack2(acc[u][j][2], acc[u][j][3])};
+  for (;;) {
+    uint32_t xr[kSPXR], xmask;  // per step, not carried round the loop
+    // the step after this one, and what it reads that the ring does not hold: two
+    // rows inside a band, six at the start of the workgroup's next band, nothing at its end
+    const bool first = pi == band.p0;
+    const int n = band.n;
+    stemplan::StemBand nband = band;
+    int nb = b, npi = pi + 1, frow = 2 * pi + 5, fcnt = 2;
+    if (npi == band.p1) {
+      nb = b + (int)gridDim.x;
+      fcnt = 0;
+      if (nb < plan.nbands) {
+        nband = stemplan::stem_band(plan, PH, nb);
+        npi = nband.p0; frow = 2 * npi - 1; fcnt = 6;
       }
     }
-    __syncthreads();
-    // 3x3/s2 window (rows of the task that exist, columns 2j-1 .. 2j+1)
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const int it = t + kSPThreads * k, j = it >> 3, q = it & 7;
-      if (j >= PW) continue;
-      float pm[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) pm[e] = -INFINITY;
-#pragma unroll
-      for (int rl = 0; rl < 3; ++rl) {
-        if (r0 + rl < 0 || r0 + rl >= OH) continue;
-#pragma unroll
-        for (int dc = -1; dc <= 1; ++dc) {
-          const int c = 2 * j + dc;
-          if (c < 0 || c >= OW) continue;
-          float e[8];
-          unpack8(*reinterpret_cast<const u32x4*>(sR + rl * (kSPMaxOW * 128) + c * 128 + ((q ^ (c & 7)) << 4)), e);
-#pragma unroll
-          for (int u = 0; u < 8; ++u) pm[u] = fmaxf(pm[u], e[u]);
-        }
-      }
-      u32x4 o = pack8(pm);  // exact: pm are bf16 values
-      if constexpr (POST) o = post_act8(o, psc, psh);
-      *reinterpret_cast<u32x4*>(y + ((int64_t)(n * PH + pi) * PW + j) * 64 + q * 8) = o;
+    if (fcnt) stem_fetch<DIRECT>(in, nband.n, frow, fcnt, H, W, HS, WS, t, xr, xmask);  // lands behind the MFMAs
+    if (first)
+      stem_rows<3>(sW, sX, sR, 2 * pi - 1, MT, wave, fr, fk);
+    else
+      stem_rows<2>(sW, sX, sR, 2 * pi, MT, wave, fr, fk);
+    __syncthreads();  // stem rows stored; every wave done reading the ring
+    if (!fcnt) {
+      stem_pool_row<POST>(sR, y, n, pi, OH, OW, PH, PW, t, psc, psh);
+      break;
     }
-    if (next < tasks) {
-      __syncthreads();  // every wave done with the slab and the row buffers
-      store_slab(xr);
-      __syncthreads();
-    }
+    // the ring first: its loads landed behind the MFMAs, and the pooled row's stores then stay
+    // in flight across the barrier.  One vmcnt(0) for all of them (nothing else is pending
+    // here) instead of the compiler's wait per register in each predicated store.
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) only
+    stem_ring_store<DIRECT>(sX, frow, fcnt, WS, t, xr, xmask);
+    stem_pool_row<POST>(sR, y, n, pi, OH, OW, PH, PW, t, psc, psh);
+    __syncthreads();  // ring filled; every wave done with the row buffers
+    b = nb; band = nband; pi = npi;
   }
 }
 
@@ -2532,6 +2671,8 @@ VGPU_API void vgpu_conv_set_tile_m(int bm) { g_forced_bm = bm; }
 VGPU_API void vgpu_conv_set_big(int mode) { g_forced_big = mode; }  // -1 env/heuristic, 0 off, 1 when eligible
 VGPU_API void vgpu_conv_set_halo(int mode) { g_forced_halo = mode; }  // -1 env, 0 off, 1 on, 2/3 BM 256/128
 VGPU_API unsigned long long vgpu_conv_halo_launches() { return g_halo_launches; }
+// Test / A-B knob of the fused stem: pooled rows per band (0 = heuristic, 1 = one pooled row per band).
+VGPU_API void vgpu_stem_set_band(int rows) { g_stem_band = rows < 0 ? 0 : rows; }
 
 namespace {
 // A vgpu_conv23* call: conv2 (a: x, w, bias, shape), conv3 (b: w, y, res; post: qscale / qshift; shortcut
@@ -2835,28 +2976,39 @@ VGPU_API int vgpu_conv2d_nhwc_bn(const void* x, const void* w, void* y, const vo
 
 
 // NHWC bf16 max pool (k×k window, stride, symmetric zero-excluded padding), 16 B per lane.
-// Fused stem: X [N][HS][WS][16] (space-to-depth input), w [64][4][4][16] →
-// y [N][PH][PW][64] = maxpool3x3/s2/p1(conv4x4/s1(X, w)), bf16 NHWC.
-static int stem_pool_impl(const void* X, const void* w, void* y, const float* qs, const float* qt, int N, int HS,
-                          int WS, hipStream_t s) {
+// Fused stem: y [N][PH][PW][64] = maxpool3x3/s2/p1(conv4x4/s1(X, w)), bf16 NHWC, with
+// w [64][4][4][16] and X [N][HS][WS][16] the space-to-depth input -- `in` itself, or
+// (direct) never stored: `in` is the image x [N][H][W][3] and X is what
+// vgpu_stem_space_to_depth(pad 3) would make of it.
+static int stem_pool_impl(const void* in, bool direct, const void* w, void* y, const float* qs, const float* qt,
+                          int N, int H, int W, int HS, int WS, hipStream_t s) {
   const int OH = HS - 3, OW = WS - 3;
   if (N < 1 || OH < 1 || OW < 1 || OW > kSPMaxOW || WS > kSPMaxWS) return -1;
-  if ((int64_t)N * HS * WS * 16 >= ((int64_t)1 << 31)) return -1;
+  // per-image offsets, and X's every offset, are 32-bit in the kernel
+  if (direct ? (int64_t)H * W * 3 >= ((int64_t)1 << 31) : (int64_t)N * HS * WS * 16 >= ((int64_t)1 << 31)) return -1;
   const int PH = (OH + 2 - 3) / 2 + 1, PW = (OW + 2 - 3) / 2 + 1;
-  if (PW * 8 > 2 * kSPThreads) return -1;
-  const int tasks = N * PH;
+  if (PW * 8 > 2 * kSPThreads || (int64_t)N * PH >= ((int64_t)1 << 31)) return -1;
   // One workgroup per CU of the device (LDS allows one), not conv_cus(): a
   // time-shared pod runs on every CU while it runs, and a masked one just
-  // queues the extra workgroups (the task loop takes any grid).
-  const int grid = device_cus() < tasks ? device_cus() : tasks;
-  hipLaunchKernelGGL(qs ? stem_pool_kernel<true> : stem_pool_kernel<false>, dim3(grid), dim3(kSPThreads), 0, s,
-                     static_cast<const uint16_t*>(X), static_cast<const uint16_t*>(w), static_cast<uint16_t*>(y), HS,
-                     WS, OH, OW, PH, PW, tasks, qs, qt);
+  // queues the extra workgroups (the band loop takes any grid).
+  thread_local int key[4] = {0, 0, 0, -1};
+  thread_local stemplan::StemPlan plan;
+  const int cus = device_cus();
+  if (key[0] != N || key[1] != PH || key[2] != cus || key[3] != g_stem_band) {
+    plan = stemplan::stem_band_plan(N, PH, cus, g_stem_band);
+    key[0] = N; key[1] = PH; key[2] = cus; key[3] = g_stem_band;
+  }
+  if (plan.nbands < 1) return -1;
+  auto kern = direct ? (qs ? stem_pool_kernel<true, true> : stem_pool_kernel<false, true>)
+                     : (qs ? stem_pool_kernel<true, false> : stem_pool_kernel<false, false>);
+  hipLaunchKernelGGL(kern, dim3(plan.grid), dim3(kSPThreads), 0, s, static_cast<const uint16_t*>(in),
+                     static_cast<const uint16_t*>(w), static_cast<uint16_t*>(y), H, W, HS, WS, OH, OW, PH, PW, plan,
+                     qs, qt);
   return (int)hipGetLastError();
 }
 
 VGPU_API int vgpu_stem_pool_nhwc(const void* X, const void* w, void* y, int N, int HS, int WS, hipStream_t s) {
-  return stem_pool_impl(X, w, y, nullptr, nullptr, N, HS, WS, s);
+  return stem_pool_impl(X, false, w, y, nullptr, nullptr, N, 0, 0, HS, WS, s);
 }
 
 // vgpu_stem_pool_nhwc with the post epilogue: y = relu(pool·qs[c] + qt[c]), qs/qt
@@ -2864,7 +3016,17 @@ VGPU_API int vgpu_stem_pool_nhwc(const void* X, const void* w, void* y, int N, i
 VGPU_API int vgpu_stem_pool_post_nhwc(const void* X, const void* w, void* y, const float* qs, const float* qt,
                                       int N, int HS, int WS, hipStream_t s) {
   if (!qs || !qt) return -1;
-  return stem_pool_impl(X, w, y, qs, qt, N, HS, WS, s);
+  return stem_pool_impl(X, false, w, y, qs, qt, N, 0, 0, HS, WS, s);
+}
+
+// The fused stem on the image itself: x [N][H][W][3] bf16 (2-byte aligned), the
+// 7x7/s2/p3 stem as w [64][4][4][16] (stem_weight_s2d), then the 3x3/s2/p1 max
+// pool; qs/qt both null: no post epilogue.  Returns -1, nothing launched, for
+// shapes the kernel does not take (stem rows wider than 176: W > 352).
+VGPU_API int vgpu_stem_pool_x_nhwc(const void* x, const void* w, void* y, const float* qs, const float* qt, int N,
+                                   int H, int W, hipStream_t s) {
+  if (H < 1 || W < 1 || W > 2 * kSPMaxOW || !qs != !qt) return -1;
+  return stem_pool_impl(x, true, w, y, qs, qt, N, H, W, (H - 1) / 2 + 4, (W - 1) / 2 + 4, s);
 }
 
 VGPU_API int vgpu_maxpool_nhwc(const void* x, void* y, int N, int H, int W, int C, int k, int stride,

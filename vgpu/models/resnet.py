@@ -147,8 +147,10 @@ class FusedResNetV2Inference(nn.Module):
     fused in — the block-entry BN+ReLU as the prologue of an identity block's
     conv1, folded-BN bias + ReLU as the epilogue of conv1/conv2, the residual
     add as the epilogue of conv3 — so a bottleneck is 3 (or 4) kernels.  The
-    7x7/s2 stem runs as space-to-depth + a 4x4 narrow-C MFMA conv with its
-    max-pool fused; the final BN+ReLU+global-mean is a hand-written kernel too.
+    7x7/s2 stem runs as a 4x4 narrow-C MFMA conv on the space-to-depth form of
+    the image, gathered inside the kernel, with its max-pool fused
+    (VGPU_STEM_DIRECT=0: a separate space-to-depth kernel first, same logits);
+    the final BN+ReLU+global-mean is a hand-written kernel too.
 
     preact=True (default): the tensor that enters a projection block (the first
     block of a stage) is read only by that block's shortcut and conv1, both
@@ -186,6 +188,8 @@ class FusedResNetV2Inference(nn.Module):
         # ... and a stride-1 projection shortcut (block 0) computed inside that tail on the
         # pre-activated input, its output never stored (VGPU_FUSE_SC=0 or fuse_sc=False disables)
         self.fuse_sc = (os.environ.get("VGPU_FUSE_SC", "1") != "0") if fuse_sc is None else bool(fuse_sc)
+        # the stem kernel reads the image itself; VGPU_STEM_DIRECT=0: space-to-depth tensor first (A/B)
+        self.stem_direct = os.environ.get("VGPU_STEM_DIRECT", "1") != "0"
         from vgpu.ops.fused import bn_scale_shift
         m = m.eval()
         dt = m.stem.weight.dtype
@@ -226,9 +230,13 @@ class FusedResNetV2Inference(nn.Module):
     def _forward_native(self, x: torch.Tensor) -> torch.Tensor:
         from vgpu.ops import conv as C
         x = x.contiguous(memory_format=torch.channels_last)
-        X = C.stem_space_to_depth(x)
-        # stem conv + max pool, one kernel; pre-activated for block 0 where the kernel takes the shape
-        x, pre = _maybe_post(functools.partial(C.stem_pool_s2d, X, self.stem_w_s2d), self._post_for(0))
+        # stem conv + max pool, one kernel on the image itself; pre-activated for block 0 where the
+        # kernel takes the shape
+        if self.stem_direct:
+            stem = functools.partial(C.stem_pool, x, self.stem_w_s2d)
+        else:
+            stem = functools.partial(C.stem_pool_s2d, C.stem_space_to_depth(x), self.stem_w_s2d)
+        x, pre = _maybe_post(stem, self._post_for(0))
         x, _ = self._blocks_native(x, 0, len(self.blocks), pre)
         return self.fc(C.scale_shift_relu_mean(x, *self.out_ss))
 

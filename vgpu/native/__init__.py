@@ -93,6 +93,11 @@ def load_kernels() -> ctypes.CDLL:
     # "post" epilogue producers (the next projection block's entry BN+ReLU stored in place of y)
     lib.vgpu_stem_pool_post_nhwc.argtypes = [vp] * 5 + [ci] * 3 + [vp]
     lib.vgpu_stem_pool_post_nhwc.restype = ci
+    # the fused stem on the image itself (no space-to-depth tensor); qs / qt null: no post
+    lib.vgpu_stem_pool_x_nhwc.argtypes = [vp] * 5 + [ci] * 3 + [vp]
+    lib.vgpu_stem_pool_x_nhwc.restype = ci
+    lib.vgpu_stem_set_band.argtypes = [ci]
+    lib.vgpu_stem_set_band.restype = None
     lib.vgpu_conv23_post_nhwc.argtypes = [vp] * 8 + [ci] * 5 + [vp]
     lib.vgpu_conv23_post_nhwc.restype = ci
     lib.vgpu_conv2d_post_nhwc_ws.argtypes = [vp] * 6 + [ci] * 6 + [vp, ctypes.c_int64, vp]

@@ -307,11 +307,37 @@ def stem_conv(x: torch.Tensor, w_s2d: torch.Tensor, k: int = 7, pad: int = 3) ->
 
 def stem_pool(x: torch.Tensor, w_s2d: torch.Tensor, k: int = 7, pad: int = 3,
               post: tuple[torch.Tensor, torch.Tensor] | None = None) -> torch.Tensor | None:
-    """maxpool3s2(stem_conv(x, w_s2d)) in one kernel (the stem activation never
-    reaches HBM); bit-identical to the two-kernel path, which it falls back to
-    for shapes the fused kernel does not take (stem rows wider than 176).
-    post: see stem_pool_s2d."""
+    """maxpool3s2(stem_conv(x, w_s2d)) in one kernel that reads the image itself
+    (neither the space-to-depth input nor the stem activation reaches HBM);
+    bit-identical to the two-kernel path.  For shapes that kernel does not take
+    (stem rows wider than 176) this is stem_pool_s2d on the space-to-depth
+    input, with its answers.  post: see stem_pool_s2d."""
+    _nhwc(x, "x")
+    n, c, h, w = x.shape
+    if c != 3:
+        raise ValueError("stem input must have 3 channels")
+    if k == 7 and pad == 3 and tuple(w_s2d.shape) == (64, 16, 4, 4):
+        _nhwc(w_s2d, "w_s2d")
+        if post is not None:
+            _check_post(post, 64)
+        ph, pw = out_hw(*out_hw(h, w, 7, 2, 3), 3, 2, 1)
+        out = torch.empty((n, 64, ph, pw), dtype=x.dtype, device=x.device, memory_format=_CL)
+        qs, qt = post if post is not None else (None, None)
+        rc = load_kernels().vgpu_stem_pool_x_nhwc(_ptr(x), _ptr(w_s2d), _ptr(out), _ptr(qs), _ptr(qt), n, h, w,
+                                                  _stream())
+        if rc == 0:
+            return out
+        if rc != -1:
+            raise RuntimeError(f"vgpu_stem_pool_x_nhwc: error {rc}")
+        if post is not None:
+            return None  # the X entry has the same limit: nothing launched
     return stem_pool_s2d(stem_space_to_depth(x, k, pad), w_s2d, post=post)
+
+
+def set_stem_band(rows: int) -> None:
+    """Tests / A-B: pooled rows per band of the fused stem kernel (0 = heuristic,
+    1 = one pooled row per band)."""
+    load_kernels().vgpu_stem_set_band(int(rows))
 
 
 def stem_pool_s2d(X: torch.Tensor, w_s2d: torch.Tensor,
