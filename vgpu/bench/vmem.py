@@ -44,6 +44,7 @@ front for both modes (VGPU_CONTEXT_CHARGE), so both hold the same HBM.
     python -m vgpu.bench.vmem --part-d [--budget-gib 22] [--modes pager,zero_copy]
     python -m vgpu.bench.vmem --part-e [--budget-gib 11.5] [--context-charge-mib 0]
     python -m vgpu.bench.vmem --part-r [--tokens 128] [--windows 6]    (resident decode_static / decode_native A/B)
+    python -m vgpu.bench.vmem --part-p [--prompt 2048] [--windows 6]   (resident forward / prefill_native A/B)
 
 --native-decode: the graph-captured decode step of parts D and E is
 Llama.decode_native (native/kernels/decode.hip + the skinny GEMV) instead of
@@ -411,6 +412,59 @@ def part_r(tokens: int, ctx: int, windows: int) -> dict:
     return out
 
 
+def part_p(prompt: int, windows: int) -> dict:
+    """Resident prompt processing, no shim, B = 1: the eager `forward(tokens,
+    kv, 0)` against `prefill_native(tokens, kv, 0)` on one set of weights,
+    windows (one prompt each) alternating in one process so that both see the
+    same machine.  The same tokens go through both; their last-token logits are compared."""
+    import statistics
+
+    import torch
+    from vgpu.models.llama import Llama, LlamaConfig
+    cfg = LlamaConfig.llama3_8b()
+    if not 1 <= prompt <= cfg.max_seq:
+        raise SystemExit(f"--prompt {prompt}: expected 1 .. {cfg.max_seq}")
+    torch.manual_seed(1)
+    with torch.device("meta"):
+        m = Llama(cfg)
+    m = m.to(torch.bfloat16).to_empty(device="cuda")
+    with torch.no_grad():
+        for p_ in m.parameters():
+            p_.normal_(0, 0.02)
+    m.eval()
+    dev = torch.device("cuda")
+    kv = {"eager": _kv(cfg, prompt, dev), "native": _kv(cfg, prompt, dev)}
+    tokens = torch.randint(0, cfg.vocab, (1, prompt), device=dev)
+
+    def run(name):
+        with torch.inference_mode():
+            return m(tokens, kv[name], 0) if name == "eager" else m.prefill_native(tokens, kv[name], 0)
+
+    logits = {}
+    for name in kv:
+        for _ in range(2):  # warm: allocator, kernel load, GEMM plans
+            logits[name] = run(name).float()
+    torch.cuda.synchronize()
+    a, b = logits["eager"], logits["native"]
+    kdiff = max((ke.float() - kn.float()).abs().max().item() for (ke, _), (kn, _) in zip(kv["eager"], kv["native"]))
+    out = {"prompt_tokens": prompt,
+           "logits_last": {"max_abs_eager": round(a.abs().max().item(), 4),
+                           "max_abs_diff": round((a - b).abs().max().item(), 4),
+                           "argmax_equal": bool(a.argmax() == b.argmax())},
+           "k_cache_max_abs_diff": round(kdiff, 4)}
+    series = {name: [] for name in kv}
+    for _ in range(windows):
+        for name in kv:
+            torch.cuda.synchronize()
+            t0 = time.time()
+            run(name)
+            torch.cuda.synchronize()
+            series[name].append(round(prompt / (time.time() - t0), 1))
+    for name, s in series.items():
+        out[name] = {"tok_s": s, "median": statistics.median(s), "min": min(s), "max": max(s)}
+    return out
+
+
 def run_pod_child(part: str, budget_gib: float, migrate: bool, args: list[str], timeout: float = 1500,
                   context_mib: int = 0) -> dict:
     from vgpu.native import ensure_built, preload_env
@@ -470,6 +524,9 @@ def main(argv=None) -> int:
                     help="book this much runtime context at first use (both modes; see Part E)")
     ap.add_argument("--part-r", action="store_true",
                     help="resident graph decode, no shim: decode_static against decode_native, alternating windows")
+    ap.add_argument("--part-p", action="store_true",
+                    help="resident prompt processing, no shim: forward against prefill_native, alternating windows")
+    ap.add_argument("--prompt", type=int, default=2048, help="prompt tokens of part P")
     ap.add_argument("--native-decode", action="store_true",
                     help="parts D and E capture Llama.decode_native (the project's kernels) instead of decode_static")
     ap.add_argument("--skip-a", action="store_true")
@@ -489,6 +546,9 @@ def main(argv=None) -> int:
         return 0
     if a.part_r:
         print("VMEM_R " + json.dumps(part_r(a.tokens, a.ctx, a.windows)), flush=True)
+        return 0
+    if a.part_p:
+        print("VMEM_P " + json.dumps(part_p(a.prompt, a.windows)), flush=True)
         return 0
     if a.part_d or a.part_e:
         part = "d" if a.part_d else "e"

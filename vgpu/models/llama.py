@@ -202,6 +202,58 @@ class Llama(nn.Module):
         D.gemv(h, self.head.weight, logits)
         return logits.view(B, 1, cfg.vocab)
 
+    @torch.no_grad()
+    def prefill_native(self, tokens: torch.Tensor, kv_caches, start: int = 0) -> torch.Tensor:
+        """`forward(tokens [B, S], kv_caches, start)` on the native kernels
+        (vgpu.ops.prefill): the projections on the bf16 MFMA GEMM, RoPE and
+        the cache write for all S tokens in one launch, causal grouped-query
+        flash attention reading K / V in place.  Writes cache rows start ..
+        start + S - 1 and attends to rows 0 .. start + i, so a prompt may come
+        in chunks; `start` is a host int (not graph-replayable at another
+        position).  bf16 weights and contiguous bf16 caches on the GPU,
+        head_dim 64 or 128, dim / ffn / qkv width / vocab multiples of 64;
+        anything else raises ValueError.  Returns the last token's logits
+        [B, 1, vocab]."""
+        from vgpu.ops import decode as D, prefill as P
+        P.check_llama_prefill(self, tokens, kv_caches, start)
+        cfg = self.cfg
+        (B, S), dev = tokens.shape, tokens.device
+        H, KVH, hd = cfg.heads, cfg.kv_heads, cfg.dim // cfg.heads
+        rows = B * S
+        cos, sin = self.rope(dev)
+
+        def buf(*shape):
+            return torch.empty(shape, dtype=torch.bfloat16, device=dev)
+
+        x = self.embed(tokens).view(rows, cfg.dim)  # the residual stream, updated in place
+        h, qkv, q = buf(rows, cfg.dim), buf(rows, (H + 2 * KVH) * hd), buf(B, S, H, hd)
+        att, ao, mlp = buf(B, S, H * hd), buf(rows, cfg.dim), buf(rows, cfg.dim)
+        gu, act = buf(rows, 2 * cfg.ffn), buf(rows, cfg.ffn)
+        scale = hd ** -0.5
+        delta = None
+        for layer, (kc, vc) in zip(self.layers, kv_caches):
+            a = layer.attn
+            D.add_rmsnorm(x, delta, layer.norm1.weight, h, layer.norm1.eps)
+            P.gemm(h, a.wqkv.weight, qkv)
+            P.rope_kv_write_seq(qkv, cos, sin, start, q, kc, vc)
+            P.attn_prefill(q, kc, vc, start, att, scale)
+            P.gemm(att.view(rows, H * hd), a.wo.weight, ao)
+            D.add_rmsnorm(x, ao, layer.norm2.weight, h, layer.norm2.eps)
+            P.gemm(h, layer.w13.weight, gu)
+            D.swiglu(gu, act)
+            P.gemm(act, layer.w2.weight, mlp)
+            delta = mlp
+        # only each sequence's last row goes through the final norm and the head
+        xl = x.view(B, S, cfg.dim)[:, -1].contiguous()
+        dl = delta.view(B, S, cfg.dim)[:, -1].contiguous() if delta is not None else None
+        hl, logits = buf(B, cfg.dim), buf(B, cfg.vocab)
+        D.add_rmsnorm(xl, dl, self.norm.weight, hl, self.norm.eps)
+        if B in D.BATCHES:
+            D.gemv(hl, self.head.weight, logits)
+        else:
+            P.gemm(hl, self.head.weight, logits)
+        return logits.view(B, 1, cfg.vocab)
+
     def new_kv_cache(self, batch: int, seq: int, dtype=torch.bfloat16, device=None):
         hd = self.cfg.dim // self.cfg.heads
         shape = (batch, self.cfg.kv_heads, seq, hd)
