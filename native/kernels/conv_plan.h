@@ -97,6 +97,7 @@ ConvPlan conv_plan(const Req& a, int KS, int64_t ws_bytes, const ConvKnobs& k, b
   if (Cout % 64 || a.stride < 1 || a.pad < 0 || a.N < 1) return p;
   const int OH = out_size(a.H, KS, a.stride, a.pad), OW = out_size(a.W, KS, a.stride, a.pad);
   if (OH < 1 || OW < 1 || (stats && (narrow || pro))) return p;
+  if (narrow && has_res) return p;  // the narrow kernels have no residual form: refuse, never drop it
   if (a.res_stride == 2 && (int64_t)a.N * ((OH + 1) / 2) * ((OW + 1) / 2) * Cout * 2 >= ((int64_t)1 << 31)) return p;
   // Post epilogue: the 1x1 + residual LDS-DMA kernels (and their split-K reduce) only.
   if (post && (KS != 1 || pro || !has_res || stats || a.gmask || a.act != 0 || a.bias)) return p;
