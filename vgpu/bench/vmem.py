@@ -43,12 +43,18 @@ front for both modes (VGPU_CONTEXT_CHARGE), so both hold the same HBM.
     python -m vgpu.bench.vmem [--spill-gib 8] [--budget-gib 8] [--tokens 16] [--part-c]
     python -m vgpu.bench.vmem --part-d [--budget-gib 22] [--modes pager,zero_copy]
     python -m vgpu.bench.vmem --part-e [--budget-gib 11.5] [--context-charge-mib 0]
-    python -m vgpu.bench.vmem --part-r [--tokens 128] [--windows 6]    (resident decode_static / decode_native A/B)
+    python -m vgpu.bench.vmem --part-r [--tokens 128] [--windows 6] [--fp8]   (resident decode_static / decode_native
+                                                                       [/ LlamaFp8.decode_native] A/B)
     python -m vgpu.bench.vmem --part-p [--prompt 2048] [--windows 6]   (resident forward / prefill_native A/B)
 
 --native-decode: the graph-captured decode step of parts D and E is
 Llama.decode_native (native/kernels/decode.hip + the skinny GEMV) instead of
 stock PyTorch.  Off by default, so earlier records stay comparable.
+
+--fp8 (with --native-decode in parts D and E, or with --part-r): the model is
+converted to LlamaFp8 (e4m3 codes and one power-of-two scale per output row for
+every projection, native/kernels/gemv_fp8.hip) and its bf16 Linear weights are
+freed: half the bytes to hold, to page and to stream per token.
 """
 from __future__ import annotations
 
@@ -294,17 +300,26 @@ def _stats_fn():
 class GraphDecoder:
     """A Llama-3-8B instance with its decode step captured as one hipGraph."""
 
-    def __init__(self, cfg, ctx: int, seed: int, native: bool = False):
+    def __init__(self, cfg, ctx: int, seed: int, native: bool = False, fp8: bool = False):
         import torch
-        from vgpu.models.llama import Llama
+        from vgpu.models.llama import Llama, LlamaFp8
+        if fp8 and not native:
+            raise ValueError("fp8 weights decode on the native kernels only (--fp8 goes with --native-decode)")
         torch.manual_seed(seed)
+        torch.cuda.synchronize()
+        before = torch.cuda.memory_allocated()
         with torch.device("meta"):
-            m = Llama(cfg)
-        self.m = m.to(torch.bfloat16).to_empty(device="cuda")
+            self.m = Llama(cfg)
+        self.m = self.m.to(torch.bfloat16).to_empty(device="cuda")
         with torch.no_grad():
             for p_ in self.m.parameters():
                 p_.normal_(0, 0.02)
+            del p_  # the loop variable would keep the head's bf16 weight alive past the conversion
         self.m.eval()
+        if fp8:  # quantise Linear by Linear; the bf16 model goes when the name is rebound (no other name holds it)
+            self.m = LlamaFp8.from_llama(self.m)
+            torch.cuda.empty_cache()  # hand the bf16 weights' HBM back, not just to the allocator's cache
+        self.weight_bytes = torch.cuda.memory_allocated() - before
         self.kv = _kv(cfg, ctx, torch.device("cuda"))
         self.tok = torch.randint(0, cfg.vocab, (1, 1), device="cuda")
         self.pos = torch.zeros(1, dtype=torch.long, device="cuda")
@@ -334,7 +349,8 @@ class GraphDecoder:
         return round(tokens / (time.time() - t0), 2)
 
 
-def part_d_child(tokens: int, ctx: int, windows: int, idle_s: float, native: bool = False) -> dict:
+def part_d_child(tokens: int, ctx: int, windows: int, idle_s: float, native: bool = False,
+                 fp8: bool = False) -> dict:
     """Runs in the pod (libvgpu.so, oversubscribed, physical budget)."""
     import torch
     from vgpu.models.llama import LlamaConfig
@@ -342,13 +358,13 @@ def part_d_child(tokens: int, ctx: int, windows: int, idle_s: float, native: boo
     cfg = LlamaConfig.llama3_8b()
     out = {}
     t0 = time.time()
-    a = GraphDecoder(cfg, ctx, 1, native)
+    a = GraphDecoder(cfg, ctx, 1, native, fp8)
     out["load_a_s"] = round(time.time() - t0, 2)
     out["a_first"] = [a.window(tokens) for _ in range(2)]
     out["after_a"] = stats()
     time.sleep(idle_s)  # A idles: its ranges go cold
     t0 = time.time()
-    b = GraphDecoder(cfg, ctx, 2, native)
+    b = GraphDecoder(cfg, ctx, 2, native, fp8)
     out["load_b_s"] = round(time.time() - t0, 2)
     out["after_load_b"] = stats()
     series = []
@@ -367,27 +383,31 @@ def part_d_child(tokens: int, ctx: int, windows: int, idle_s: float, native: boo
     return out
 
 
-def part_e_child(tokens: int, ctx: int, windows: int, native: bool = False) -> dict:
+def part_e_child(tokens: int, ctx: int, windows: int, native: bool = False, fp8: bool = False) -> dict:
     from vgpu.models.llama import LlamaConfig
     stats = _stats_fn()
-    a = GraphDecoder(LlamaConfig.llama3_8b(), ctx, 1, native)
-    out = {"after_load": stats()}
+    a = GraphDecoder(LlamaConfig.llama3_8b(), ctx, 1, native, fp8)
+    out = {"after_load": stats(), "weight_bytes": a.weight_bytes}
     t_rel = time.time()
     out["serving"] = [[round(time.time() - t_rel, 2), a.window(tokens)] for _ in range(windows)]
     out["final"] = stats()
     return out
 
 
-def part_r(tokens: int, ctx: int, windows: int) -> dict:
+def part_r(tokens: int, ctx: int, windows: int, fp8: bool = False) -> dict:
     """Resident graph decode, no shim: decode_static against decode_native on
     one model's worth of weights each (same seed), windows alternating in one
-    process so that both see the same machine."""
+    process so that both see the same machine.  fp8: a third series,
+    native_fp8 (LlamaFp8.decode_native on the same weights quantised), its
+    position-0 logits against bf16 native, and each decoder's weight bytes."""
     import statistics
 
     import torch
     from vgpu.models.llama import LlamaConfig
     cfg = LlamaConfig.llama3_8b()
     dec = {"static": GraphDecoder(cfg, ctx, 1), "native": GraphDecoder(cfg, ctx, 1, native=True)}
+    if fp8:
+        dec["native_fp8"] = GraphDecoder(cfg, ctx, 1, native=True, fp8=True)
     for d in dec.values():  # the captured step at position 0 on an empty cache: the two paths' logits
         for k, v in d.kv:
             k.zero_()
@@ -399,7 +419,15 @@ def part_r(tokens: int, ctx: int, windows: int) -> dict:
     out = {"ctx": ctx, "window_tokens": tokens,
            "logits_pos0": {"max_abs_static": round(a.abs().max().item(), 4),
                            "max_abs_diff": round((a - b).abs().max().item(), 4),
-                           "argmax_equal": bool(a.argmax() == b.argmax())}}
+                           "argmax_equal": bool(a.argmax() == b.argmax())},
+           "weight_bytes": {name: d.weight_bytes for name, d in dec.items()}}
+    if fp8:
+        c = dec["native_fp8"].out.float()
+        out["logits_pos0_fp8"] = {"max_abs_native": round(b.abs().max().item(), 4),
+                                  "max_abs_diff": round((b - c).abs().max().item(), 4),
+                                  "rms_diff": round((b - c).pow(2).mean().sqrt().item(), 4),
+                                  "rms_native": round(b.pow(2).mean().sqrt().item(), 4),
+                                  "argmax_equal": bool(b.argmax() == c.argmax())}
     for d in dec.values():
         d.window(tokens)  # warm
         d.n = 0
@@ -529,9 +557,13 @@ def main(argv=None) -> int:
     ap.add_argument("--prompt", type=int, default=2048, help="prompt tokens of part P")
     ap.add_argument("--native-decode", action="store_true",
                     help="parts D and E capture Llama.decode_native (the project's kernels) instead of decode_static")
+    ap.add_argument("--fp8", action="store_true",
+                    help="fp8 (e4m3) projection weights: with --native-decode in parts D and E; a third series in part R")
     ap.add_argument("--skip-a", action="store_true")
     ap.add_argument("--skip-b", action="store_true")
     a = ap.parse_args(argv)
+    if a.fp8 and not (a.part_r or a.native_decode):
+        ap.error("--fp8 goes with --native-decode (parts D and E) or --part-r")
     if a.child_a:
         print("VMEM_A " + json.dumps(part_a_child(a.spill_gib)), flush=True)
         return 0
@@ -539,13 +571,13 @@ def main(argv=None) -> int:
         print("VMEM_C " + json.dumps(part_c_child(a.tokens, a.ctx, a.windows)), flush=True)
         return 0
     if a.child_d:
-        print("VMEM_D " + json.dumps(part_d_child(a.tokens, a.ctx, a.windows, a.idle_s, a.native_decode)), flush=True)
+        print("VMEM_D " + json.dumps(part_d_child(a.tokens, a.ctx, a.windows, a.idle_s, a.native_decode, a.fp8)), flush=True)
         return 0
     if a.child_e:
-        print("VMEM_E " + json.dumps(part_e_child(a.tokens, a.ctx, a.windows, a.native_decode)), flush=True)
+        print("VMEM_E " + json.dumps(part_e_child(a.tokens, a.ctx, a.windows, a.native_decode, a.fp8)), flush=True)
         return 0
     if a.part_r:
-        print("VMEM_R " + json.dumps(part_r(a.tokens, a.ctx, a.windows)), flush=True)
+        print("VMEM_R " + json.dumps(part_r(a.tokens, a.ctx, a.windows, a.fp8)), flush=True)
         return 0
     if a.part_p:
         print("VMEM_P " + json.dumps(part_p(a.prompt, a.windows)), flush=True)
@@ -555,11 +587,13 @@ def main(argv=None) -> int:
         out = {"config": f"amd.com/gpumem=400000 (MiB), VGPU_OVERSUBSCRIBE=true, physical budget {a.budget_gib} GiB, "
                          + ("two Llama-3-8B bf16 (model switch)" if a.part_d else "one Llama-3-8B bf16")
                          + ", decode step as one hipGraph replay, ctx " + str(a.ctx)
-                         + (", native decode kernels" if a.native_decode else "")}
+                         + (", native decode kernels" if a.native_decode else "")
+                         + (", fp8 (e4m3) projection weights" if a.fp8 else "")}
         for mode in a.modes.split(","):
             out[mode] = run_pod_child(part, a.budget_gib, mode == "pager",
                                       ["--tokens", str(a.tokens), "--ctx", str(a.ctx), "--windows", str(a.windows),
-                                       "--idle-s", str(a.idle_s)] + (["--native-decode"] if a.native_decode else []),
+                                       "--idle-s", str(a.idle_s)] + (["--native-decode"] if a.native_decode else [])
+                                      + (["--fp8"] if a.fp8 else []),
                                       context_mib=a.context_charge_mib)
             print(f"VMEM_{part.upper()}_RUN " + json.dumps(out[mode]), flush=True)
         print(json.dumps(out), flush=True)

@@ -108,6 +108,87 @@ class Block(nn.Module):
         return x + self.w2(F.silu(g) * u)
 
 
+LINEARS = ("wqkv", "wo", "w13", "w2")  # the projections of a layer, in the order a step applies them
+
+
+def _decode_step(cfg, x, norms, norm_f, rope, kv_caches, pos, linear):
+    """The body of a native decode step (vgpu.ops.decode), shared by Llama and
+    LlamaFp8.  x: the embedded tokens [B, 1, dim]; norms: per layer (norm1,
+    norm2) weights; `linear(name, i, x, y)` applies projection `name` (one of
+    LINEARS, or "head" with i None) of layer i to x [B, K] into y [B, N]: the
+    one thing the two models do differently."""
+    from vgpu.ops import decode as D
+    B, dev = x.shape[0], x.device
+    H, KVH, hd = cfg.heads, cfg.kv_heads, cfg.dim // cfg.heads
+    ctx = kv_caches[0][0].shape[2] if kv_caches else 1
+    cos, sin = rope
+
+    def buf(*shape, dtype=torch.bfloat16):
+        return torch.empty(shape, dtype=dtype, device=dev)
+
+    x = x.view(B, cfg.dim)  # the residual stream, updated in place
+    h, qkv, q = buf(B, cfg.dim), buf(B, (H + 2 * KVH) * hd), buf(B, H, hd)
+    att, ao, mlp = buf(B, H * hd), buf(B, cfg.dim), buf(B, cfg.dim)
+    gu, act = buf(B, 2 * cfg.ffn), buf(B, cfg.ffn)
+    ws = buf(D.attn_workspace_bytes(B, H, hd, ctx) // 4, dtype=torch.float32)
+    scale = hd ** -0.5
+    delta = None
+    for i, ((norm1, norm2), (kc, vc)) in enumerate(zip(norms, kv_caches)):
+        D.add_rmsnorm(x, delta, norm1, h, cfg.eps)
+        linear("wqkv", i, h, qkv)
+        D.rope_kv_write(qkv, cos, sin, pos, q, kc, vc)
+        D.attn_decode(q, kc, vc, pos, att, ws, scale)
+        linear("wo", i, att, ao)
+        D.add_rmsnorm(x, ao, norm2, h, cfg.eps)
+        linear("w13", i, h, gu)
+        D.swiglu(gu, act)
+        linear("w2", i, act, mlp)
+        delta = mlp
+    D.add_rmsnorm(x, delta, norm_f, h, cfg.eps)
+    logits = buf(B, cfg.vocab)
+    linear("head", None, h, logits)
+    return logits.view(B, 1, cfg.vocab)
+
+
+def _prefill(cfg, x, norms, norm_f, rope, kv_caches, start, linear):
+    """The body of a native prompt pass (vgpu.ops.prefill), shared by Llama and
+    LlamaFp8; arguments as _decode_step's, x [B, S, dim].  "head" gets each
+    sequence's last row only, [B, dim]."""
+    from vgpu.ops import decode as D, prefill as P
+    (B, S), dev = x.shape[:2], x.device
+    H, KVH, hd = cfg.heads, cfg.kv_heads, cfg.dim // cfg.heads
+    rows = B * S
+    cos, sin = rope
+
+    def buf(*shape):
+        return torch.empty(shape, dtype=torch.bfloat16, device=dev)
+
+    x = x.view(rows, cfg.dim)  # the residual stream, updated in place
+    h, qkv, q = buf(rows, cfg.dim), buf(rows, (H + 2 * KVH) * hd), buf(B, S, H, hd)
+    att, ao, mlp = buf(B, S, H * hd), buf(rows, cfg.dim), buf(rows, cfg.dim)
+    gu, act = buf(rows, 2 * cfg.ffn), buf(rows, cfg.ffn)
+    scale = hd ** -0.5
+    delta = None
+    for i, ((norm1, norm2), (kc, vc)) in enumerate(zip(norms, kv_caches)):
+        D.add_rmsnorm(x, delta, norm1, h, cfg.eps)
+        linear("wqkv", i, h, qkv)
+        P.rope_kv_write_seq(qkv, cos, sin, start, q, kc, vc)
+        P.attn_prefill(q, kc, vc, start, att, scale)
+        linear("wo", i, att.view(rows, H * hd), ao)
+        D.add_rmsnorm(x, ao, norm2, h, cfg.eps)
+        linear("w13", i, h, gu)
+        D.swiglu(gu, act)
+        linear("w2", i, act, mlp)
+        delta = mlp
+    # only each sequence's last row goes through the final norm and the head
+    xl = x.view(B, S, cfg.dim)[:, -1].contiguous()
+    dl = delta.view(B, S, cfg.dim)[:, -1].contiguous() if delta is not None else None
+    hl, logits = buf(B, cfg.dim), buf(B, cfg.vocab)
+    D.add_rmsnorm(xl, dl, norm_f, hl, cfg.eps)
+    linear("head", None, hl, logits)
+    return logits.view(B, 1, cfg.vocab)
+
+
 class Llama(nn.Module):
     def __init__(self, cfg: LlamaConfig):
         super().__init__()
@@ -169,38 +250,13 @@ class Llama(nn.Module):
         anything else raises ValueError."""
         from vgpu.ops import decode as D
         D.check_llama_decode(self, tokens, kv_caches, pos)
-        cfg = self.cfg
-        B, dev = tokens.shape[0], tokens.device
-        H, KVH, hd = cfg.heads, cfg.kv_heads, cfg.dim // cfg.heads
-        ctx = kv_caches[0][0].shape[2] if kv_caches else 1
-        cos, sin = self.rope(dev)
+        lin = [(l.attn.wqkv.weight, l.attn.wo.weight, l.w13.weight, l.w2.weight) for l in self.layers]
 
-        def buf(*shape, dtype=torch.bfloat16):
-            return torch.empty(shape, dtype=dtype, device=dev)
+        def linear(name, i, x, y):
+            D.gemv(x, self.head.weight if name == "head" else lin[i][LINEARS.index(name)], y)
 
-        x = self.embed(tokens).view(B, cfg.dim)  # the residual stream, updated in place
-        h, qkv, q = buf(B, cfg.dim), buf(B, (H + 2 * KVH) * hd), buf(B, H, hd)
-        att, ao, mlp = buf(B, H * hd), buf(B, cfg.dim), buf(B, cfg.dim)
-        gu, act = buf(B, 2 * cfg.ffn), buf(B, cfg.ffn)
-        ws = buf(D.attn_workspace_bytes(B, H, hd, ctx) // 4, dtype=torch.float32)
-        scale = hd ** -0.5
-        delta = None
-        for layer, (kc, vc) in zip(self.layers, kv_caches):
-            a = layer.attn
-            D.add_rmsnorm(x, delta, layer.norm1.weight, h, layer.norm1.eps)
-            D.gemv(h, a.wqkv.weight, qkv)
-            D.rope_kv_write(qkv, cos, sin, pos, q, kc, vc)
-            D.attn_decode(q, kc, vc, pos, att, ws, scale)
-            D.gemv(att, a.wo.weight, ao)
-            D.add_rmsnorm(x, ao, layer.norm2.weight, h, layer.norm2.eps)
-            D.gemv(h, layer.w13.weight, gu)
-            D.swiglu(gu, act)
-            D.gemv(act, layer.w2.weight, mlp)
-            delta = mlp
-        D.add_rmsnorm(x, delta, self.norm.weight, h, self.norm.eps)
-        logits = buf(B, cfg.vocab)
-        D.gemv(h, self.head.weight, logits)
-        return logits.view(B, 1, cfg.vocab)
+        return _decode_step(self.cfg, self.embed(tokens), [(l.norm1.weight, l.norm2.weight) for l in self.layers],
+                            self.norm.weight, self.rope(tokens.device), kv_caches, pos, linear)
 
     @torch.no_grad()
     def prefill_native(self, tokens: torch.Tensor, kv_caches, start: int = 0) -> torch.Tensor:
@@ -216,46 +272,153 @@ class Llama(nn.Module):
         [B, 1, vocab]."""
         from vgpu.ops import decode as D, prefill as P
         P.check_llama_prefill(self, tokens, kv_caches, start)
-        cfg = self.cfg
-        (B, S), dev = tokens.shape, tokens.device
-        H, KVH, hd = cfg.heads, cfg.kv_heads, cfg.dim // cfg.heads
-        rows = B * S
-        cos, sin = self.rope(dev)
+        lin = [(l.attn.wqkv.weight, l.attn.wo.weight, l.w13.weight, l.w2.weight) for l in self.layers]
 
-        def buf(*shape):
-            return torch.empty(shape, dtype=torch.bfloat16, device=dev)
+        def linear(name, i, x, y):
+            if name == "head":  # B rows: the GEMV where it takes the batch
+                (D.gemv if x.shape[0] in D.BATCHES else P.gemm)(x, self.head.weight, y)
+            else:
+                P.gemm(x, lin[i][LINEARS.index(name)], y)
 
-        x = self.embed(tokens).view(rows, cfg.dim)  # the residual stream, updated in place
-        h, qkv, q = buf(rows, cfg.dim), buf(rows, (H + 2 * KVH) * hd), buf(B, S, H, hd)
-        att, ao, mlp = buf(B, S, H * hd), buf(rows, cfg.dim), buf(rows, cfg.dim)
-        gu, act = buf(rows, 2 * cfg.ffn), buf(rows, cfg.ffn)
-        scale = hd ** -0.5
-        delta = None
-        for layer, (kc, vc) in zip(self.layers, kv_caches):
-            a = layer.attn
-            D.add_rmsnorm(x, delta, layer.norm1.weight, h, layer.norm1.eps)
-            P.gemm(h, a.wqkv.weight, qkv)
-            P.rope_kv_write_seq(qkv, cos, sin, start, q, kc, vc)
-            P.attn_prefill(q, kc, vc, start, att, scale)
-            P.gemm(att.view(rows, H * hd), a.wo.weight, ao)
-            D.add_rmsnorm(x, ao, layer.norm2.weight, h, layer.norm2.eps)
-            P.gemm(h, layer.w13.weight, gu)
-            D.swiglu(gu, act)
-            P.gemm(act, layer.w2.weight, mlp)
-            delta = mlp
-        # only each sequence's last row goes through the final norm and the head
-        xl = x.view(B, S, cfg.dim)[:, -1].contiguous()
-        dl = delta.view(B, S, cfg.dim)[:, -1].contiguous() if delta is not None else None
-        hl, logits = buf(B, cfg.dim), buf(B, cfg.vocab)
-        D.add_rmsnorm(xl, dl, self.norm.weight, hl, self.norm.eps)
-        if B in D.BATCHES:
-            D.gemv(hl, self.head.weight, logits)
-        else:
-            P.gemm(hl, self.head.weight, logits)
-        return logits.view(B, 1, cfg.vocab)
+        return _prefill(self.cfg, self.embed(tokens), [(l.norm1.weight, l.norm2.weight) for l in self.layers],
+                        self.norm.weight, self.rope(tokens.device), kv_caches, start, linear)
 
     def new_kv_cache(self, batch: int, seq: int, dtype=torch.bfloat16, device=None):
         hd = self.cfg.dim // self.cfg.heads
         shape = (batch, self.cfg.kv_heads, seq, hd)
         return [(torch.empty(shape, dtype=dtype, device=device),
                  torch.empty(shape, dtype=dtype, device=device)) for _ in range(self.cfg.layers)]
+
+
+class Fp8Linear(nn.Module):
+    """A bias-free Linear's weight [N, K] as e4m3fn codes and one fp32 scale per row (vgpu.ops.fp8)."""
+
+    def __init__(self, codes: torch.Tensor, scale: torch.Tensor):
+        super().__init__()
+        self.register_buffer("codes", codes)
+        self.register_buffer("scale", scale)
+
+
+class Fp8Block(nn.Module):
+    def __init__(self, norm1, norm2, **linears):
+        super().__init__()
+        self.register_buffer("norm1", norm1)
+        self.register_buffer("norm2", norm2)
+        for name in LINEARS:
+            setattr(self, name, linears[name])
+
+
+class LlamaFp8(nn.Module):
+    """A Llama whose projection weights (wqkv, wo, w13, w2 of every layer, and
+    the head) are held in fp8: half the bytes a decode step streams and half the
+    HBM of the projections.  The embedding and the norm weights stay bf16.
+    Inference on the native kernels only; everything is a buffer."""
+
+    def __init__(self, cfg: LlamaConfig, embed, layers, norm, head):
+        super().__init__()
+        self.cfg = cfg
+        self.register_buffer("embed", embed)
+        self.layers = nn.ModuleList(layers)
+        self.register_buffer("norm", norm)
+        self.head = head
+        self._rope = None
+
+    rope = Llama.rope
+    new_kv_cache = Llama.new_kv_cache
+
+    @classmethod
+    @torch.no_grad()
+    def from_llama(cls, model: Llama, device=None) -> "LlamaFp8":
+        """Quantise `model` (on the CPU or the GPU, any floating dtype) one
+        Linear at a time, each on the device it sits on, and place the result on
+        `device` (None: where the model is): beyond the result, one weight's
+        worth of memory at the peak."""
+        from vgpu.ops import fp8 as Q
+        if not isinstance(model, Llama):
+            raise ValueError(f"model: {type(model).__name__}, expected a Llama")
+        Q.check_llama_fp8_config(model.cfg)
+
+        def keep(t):
+            return t.detach().to(device=device, dtype=torch.bfloat16).contiguous()
+
+        def lin(m, name):
+            try:
+                codes, scale = Q.quantize(m.weight)
+            except ValueError as e:
+                raise ValueError(f"{name}: {e}") from None
+            return Fp8Linear(codes.to(device), scale.to(device))
+
+        layers = []
+        for i, l in enumerate(model.layers):
+            mods = {"wqkv": l.attn.wqkv, "wo": l.attn.wo, "w13": l.w13, "w2": l.w2}
+            layers.append(Fp8Block(keep(l.norm1.weight), keep(l.norm2.weight),
+                                   **{n: lin(m, f"layers.{i}.{n}") for n, m in mods.items()}))
+        return cls(model.cfg, keep(model.embed.weight), layers, keep(model.norm.weight), lin(model.head, "head")).eval()
+
+    @torch.no_grad()
+    def dequantized(self) -> Llama:
+        """A bf16 Llama (on this model's device) holding exactly the values this model represents."""
+        from vgpu.ops import fp8 as Q
+        with torch.device("meta"):
+            m = Llama(self.cfg)
+        m = m.to(torch.bfloat16).to_empty(device=self.embed.device)
+        m.embed.weight.copy_(self.embed)
+        m.norm.weight.copy_(self.norm)
+        m.head.weight.copy_(Q.dequantize_ref(self.head.codes, self.head.scale))
+        for src, dst in zip(self.layers, m.layers):
+            dst.norm1.weight.copy_(src.norm1)
+            dst.norm2.weight.copy_(src.norm2)
+            for name, lin in (("wqkv", dst.attn.wqkv), ("wo", dst.attn.wo), ("w13", dst.w13), ("w2", dst.w2)):
+                q = getattr(src, name)
+                lin.weight.copy_(Q.dequantize_ref(q.codes, q.scale))
+        return m.eval()
+
+    def _linear(self, name, i) -> Fp8Linear:
+        return self.head if name == "head" else getattr(self.layers[i], name)
+
+    def _norms(self):
+        return [(l.norm1, l.norm2) for l in self.layers]
+
+    @torch.no_grad()
+    def decode_native(self, tokens: torch.Tensor, kv_caches, pos: torch.Tensor) -> torch.Tensor:
+        """Llama.decode_native with the fp8 GEMV (vgpu.ops.fp8.gemv_fp8) in place
+        of the bf16 one: the same ten dispatches per layer, the same caches,
+        `pos` read on the device (graph-capturable)."""
+        from vgpu.ops import fp8 as Q
+        Q.check_llama_fp8_decode(self, tokens, kv_caches, pos)
+
+        def linear(name, i, x, y):
+            q = self._linear(name, i)
+            Q.gemv_fp8(x, q.codes, q.scale, y)
+
+        return _decode_step(self.cfg, F.embedding(tokens, self.embed), self._norms(), self.norm,
+                            self.rope(tokens.device), kv_caches, pos, linear)
+
+    @torch.no_grad()
+    def prefill_native(self, tokens: torch.Tensor, kv_caches, start: int = 0) -> torch.Tensor:
+        """Llama.prefill_native over the fp8 weights: each projection's weight is
+        expanded to bf16 (vgpu.ops.fp8.dequant) into one scratch buffer, sized
+        for the largest weight and allocated once per call, and fed to the bf16
+        MFMA GEMM.  With power-of-two scales this is `dequantized()
+        .prefill_native` bit for bit.  The head takes the fp8 GEMV where that
+        takes the batch."""
+        from vgpu.ops import decode as D, fp8 as Q, prefill as P
+        Q.check_llama_fp8_prefill(self, tokens, kv_caches, start)
+        cfg = self.cfg
+        B = tokens.shape[0]
+        largest = max([q.codes.numel() for l in self.layers for q in (l.wqkv, l.wo, l.w13, l.w2)]
+                      + [0 if B in D.BATCHES else self.head.codes.numel()])
+        scratch = torch.empty(largest, dtype=torch.bfloat16, device=tokens.device)
+
+        def linear(name, i, x, y):
+            q = self._linear(name, i)
+            if name == "head" and B in D.BATCHES:
+                Q.gemv_fp8(x, q.codes, q.scale, y)
+                return
+            w = scratch[:q.codes.numel()].view(q.codes.shape)
+            Q.dequant(q.codes, q.scale, w)
+            P.gemm(x, w, y)
+
+        return _prefill(cfg, F.embedding(tokens, self.embed), self._norms(), self.norm, self.rope(tokens.device),
+                        kv_caches, start, linear)
+
