@@ -472,6 +472,42 @@ __device__ __forceinline__ void mma_k64(const char* sA, const char* sB, int arow
   mm(1);
 }
 
+// mma_k64<TM, TN, true> whose A rows come from a halo image: aoff[i] is the byte
+// offset of row tile i's fragment for the first 32-wide half, swz(row, fk) of
+// whatever halo row the lane's pixel reads at this tap; the second half is the
+// same row four slots on, which in the swizzle is that offset ^ 64.
+template <int TM, int TN>
+__device__ __forceinline__ void mma_k64_halo(const char* sH, const uint32_t (&aoff)[TM], const char* sB, int brow,
+                                             int fr, int fk, f32x4_t (&acc)[TM][TN]) {
+  bf16x8_t af[2][TM], bfr[2][TN];
+  auto rd = [&](int kk) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+      af[kk][i] = *reinterpret_cast<const bf16x8_t*>(sH + (aoff[i] ^ (uint32_t)(kk << 6)));
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+      bfr[kk][j] = *reinterpret_cast<const bf16x8_t*>(sB + swz(brow + j * 16 + fr, kk * 4 + fk));
+  };
+  auto mm = [&](int kk) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j)
+        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[kk][j], af[kk][i], acc[i][j], 0, 0, 0);
+  };
+  rd(0);
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_waitcnt(kLgkm0);
+  __builtin_amdgcn_sched_barrier(0);
+  rd(1);
+  __builtin_amdgcn_sched_barrier(0);
+  mm(0);
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_waitcnt(kLgkm0);
+  __builtin_amdgcn_sched_barrier(0);
+  mm(1);
+}
+
 // Epilogue, one row half at a time: accumulators → LDS (fp32) → 16-B
 // coalesced bias + residual + act + store.  The residual loads of a half
 // overlap its accumulator staging.  Needs (BM/2)·(BN+4)·4 bytes of LDS and a
@@ -1761,7 +1797,30 @@ __device__ __forceinline__ void tail_epilogue(const ConvArgs& a, f32x4_t (&acc)[
 // conv3 accumulators before they are staged -- the same roundings and the same
 // fp32 addition as residual = conv(x', wsc), so y and h1 are bit-identical,
 // without the shortcut's 4W-wide write and re-read.
-template <int BM, int W, bool NEXT = false, int NS1 = 3, int NT = kThreads, bool POST = false, bool SC = false>
+// HALO (stride 1, W = 64; conv_plan.h's conv23_halo_ok says which images): phase 1
+// reads conv2's A operand from a halo image, not from nine gathers.  The ring
+// form above brings the tile's BM input rows in once per filter tap (9 x 16 KB of
+// A beside 9 x 8 KB of weights per tile); with stride 1 and pad 1 the nine taps
+// of BM consecutive output pixels all lie in the contiguous flat pixel range
+// [m0 - W - 1, m0 + BM + W + 1), so that range (BM + 2W + 2 rows of 128 B: 304 at
+// the flagship's 87-wide stage 1, 38 KB) is DMA'd once into the front of phase
+// 1's region, in the swz() layout, and tile pixel i reads halo row i + kh·W + kw
+// at tap (kh, kw) -- or the halo image's last row, which no tap reaches and the DMA
+// fills with zeros, when the tap leaves the image or the row is past M.  The
+// row comes from (oh, ow) kept per pixel (validity is per pixel: a tile may
+// straddle images).  The remainder of the region is a ring of four weight
+// panels: the halo is waited for once, with panel 0, and every later step waits
+// only for a panel issued three steps earlier.  Same K order (tap major, channel
+// block minor), same MFMAs, so the accumulators hold the ring form's bits.
+// Measured on the flagship's stage-1 tails: -10 to -13 us of 110-134 us each, at
+// the level of a build that gathers A for tap 0 only; rings of three and two
+// panels were 1.7 and 4.5 us slower than four on b1 and b2 and level on b0.
+// W = 128 (stage 2, whose region leaves
+// a ring of two 16 KB panels) gained 3-6 us of 69-90, not more than the ring
+// form's round-to-round spread, and is not instantiated
+// (profiles/r11/tail_halo/README.md).
+template <int BM, int W, bool NEXT = false, int NS1 = 3, int NT = kThreads, bool POST = false, bool SC = false,
+          bool HALO = false>
 __global__ void __launch_bounds__(NT, 512 / NT) conv23_kernel(const ConvArgs a, const ConvArgs b,
                                                               const ConvArgs c) {
   constexpr int KCH = W / 64;                // conv3 K chunks (64 channels each)
@@ -1788,6 +1847,15 @@ __global__ void __launch_bounds__(NT, 512 / NT) conv23_kernel(const ConvArgs a, 
   static_assert(NT == 512 || 2 * (P + PAR) <= 160 * 1024, "conv23: two workgroups per CU");
   static_assert(!SC || (NEXT && W == 64), "shortcut in the tail: K = 64, behind the fused conv1");
   static_assert(!SC || (BM + BN2) * 128 <= EPI, "shortcut operands fit the epilogue staging area");
+  // HALO: phase 1's region holds [halo image: KCH blocks of HROWS rows | NSW weight panels] (conv_plan.h).
+  constexpr int HROWS = convplan::conv23_halo_rows(W, BM), NSW = convplan::conv23_halo_ring(W);
+  constexpr int HSTAGE = HROWS * 128, HI = HROWS * KCH / RPI, ZROW = HROWS - 1;
+  static_assert(!HALO || (NT == kThreads && NS1 == 3 && convplan::conv23_bm(W, NEXT, POST, SC) == BM),
+                "conv23 halo: the planned 256-thread tiles");
+  static_assert(!HALO || (HROWS % RPI == 0 && convplan::conv23_halo_bytes(W, BM) <= P1 &&
+                          KCH * HSTAGE + NSW * B_BYTES == convplan::conv23_halo_bytes(W, BM)),
+                "conv23 halo: image and weight ring fit the ring form's region");
+  static_assert(!HALO || (NSW >= 2 && NSW <= 4 && KCH * HSTAGE <= 65536), "conv23 halo: ring depth, 16-bit rows");
   __shared__ __attribute__((aligned(16))) char smem[P + PAR];
   char* sA2 = smem + B2_BYTES + EPI;
   float* sPar = reinterpret_cast<float*>(smem + P);
@@ -1858,7 +1926,71 @@ __global__ void __launch_bounds__(NT, 512 / NT) conv23_kernel(const ConvArgs a, 
   for (int i = 0; i < TM; ++i)
 #pragma unroll
     for (int j = 0; j < TN; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-  {
+  if constexpr (HALO) {
+    // Stride 1, pad 1: output pixel m reads input pixels m + (kh-1)·W + (kw-1) of the
+    // flat N·H·W order, so the tile's nine taps read halo rows i + kh·W + kw of the range
+    // that starts at pixel m0 - W - 1 (i: the tile-local pixel).  The halo goes first
+    // and is waited for once, with panel 0; after that a step waits only for its weight
+    // panel, issued NSW - 1 steps ahead.  Same K order as the ring (kt = tap·KCH + cb).
+    const int IW = a.W, IH = a.H;
+    char* sW = smem + KCH * HSTAGE;
+    const int live = BM + 2 * IW + 2;  // rows the taps can reach: < ZROW by conv23_halo_ok
+    const int p0 = m0 - IW - 1;
+#pragma unroll
+    for (int i = 0; i < HROWS / RPI; ++i) {
+      const int h = RPI * i + lrow, p = p0 + h;
+      const bool v = (h < live) & ((unsigned)p < (unsigned)a.M);  // the rest, the zero row among it, reads zeros
+#pragma unroll
+      for (int cb = 0; cb < KCH; ++cb)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(
+            xr, (lds_void_t*)(smem + cb * HSTAGE + (RPI * i + wave * 8) * 128), 16,
+            v ? ((uint32_t)p * W + cb * BK + lchunk * 8) * 2u : kOOB, 0, 0, 0);
+    }
+    auto issue_w = [&](int kt, int st) {
+#pragma unroll
+      for (int i = 0; i < BR; ++i)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(
+            wr, (lds_void_t*)(sW + st * B_BYTES + (RPI * i + wave * 8) * 128), 16,
+            boff + (uint32_t)((RPI * i * a.K + kt * BK) * 2), 0, 0, 0);
+    };
+#pragma unroll
+    for (int s = 0; s < NSW - 1; ++s) issue_w(s, s);
+    // (oh, ow) of the lane's pixels: a tile may straddle images, validity is per pixel.
+    int poh[TM], pow_[TM];
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+      const int m = m0 + wm * WTM + i * 16 + fr;
+      const bool ok = m < a.M;
+      const int mm = ok ? m : 0, t2 = mm / IW;
+      pow_[i] = mm - t2 * IW;
+      poh[i] = ok ? t2 % IH : -4;  // rows past M: every tap is the zero row
+    }
+    constexpr int KT = 9 * KCH;
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt) {
+      const int tap = kt / KCH, cb = kt - tap * KCH, kh = tap / 3, kw = tap - kh * 3;
+      // panel kt (and, at step 0, the halo) landed; up to NSW - 2 younger panels may fly
+      if (NSW >= 4 && kt + 2 < KT)
+        __builtin_amdgcn_s_waitcnt(vmcnt_imm(2 * BR));
+      else if (NSW >= 3 && kt + 1 < KT)
+        __builtin_amdgcn_s_waitcnt(vmcnt_imm(BR));
+      else
+        __builtin_amdgcn_s_waitcnt(vmcnt_imm(0));
+      __builtin_amdgcn_s_waitcnt(kLgkm0);
+      __builtin_amdgcn_s_barrier();  // also: every wave finished step kt-1's reads of the slot refilled next
+      if (kt + NSW - 1 < KT) issue_w(kt + NSW - 1, (kt + NSW - 1) % NSW);
+      uint32_t aoff[TM];
+#pragma unroll
+      for (int i = 0; i < TM; ++i) {
+        const bool v = ((unsigned)(poh[i] + kh - 1) < (unsigned)IH) & ((unsigned)(pow_[i] + kw - 1) < (unsigned)IW);
+        const int row = v ? wm * WTM + i * 16 + fr + kh * IW + kw : ZROW;
+        aoff[i] = (uint32_t)(cb * HSTAGE + swz(row, fk));
+      }
+      mma_k64_halo<TM, TN>(smem, aoff, sW + (kt % NSW) * B_BYTES, wn * WTN, fr, fk, acc);
+    }
+    __builtin_amdgcn_s_waitcnt(kLgkm0);
+    __builtin_amdgcn_s_barrier();  // halo and panels read out before the A image overwrites them
+  } else {
     // Two steps in flight behind the MMA, one barrier per step: step kt's wait
     // + barrier also proves every wave finished step kt-1's reads of the stage
     // that issue(kt+2) refills.
@@ -2139,6 +2271,13 @@ bool halo_enabled() {
   return !(v && (v[0] == '0' || v[0] == 'n' || v[0] == 'f'));
 }
 
+// conv23's halo form of phase 1 (VGPU_CONV23_HALO=0 keeps the ring).  Read per call:
+// a runner built after the variable changes gets the other form.
+bool conv23_halo_enabled() {
+  const char* const v = getenv("VGPU_CONV23_HALO");
+  return !(v && (v[0] == '0' || v[0] == 'n' || v[0] == 'f'));
+}
+
 // ---- Host side: knobs → plan (conv_plan.h) → one launch ----------------------
 int g_forced_bm = 0;      // vgpu_conv_set_tile_m (A/B benchmarking); 0 = heuristic
 int g_forced_big = -1;    // vgpu_conv_set_big: -1 = env VGPU_CONV_BIG / heuristic, 0 = off, 1 = whenever eligible
@@ -2146,6 +2285,8 @@ int g_forced_halo = -1;   // vgpu_conv_set_halo: -1 = env VGPU_CONV_HALO, 0 = of
 int g_forced_split = -1;  // vgpu_conv_set_splitk: -1 heuristic, 0 off, n > 1 that many splits when eligible
 unsigned long long g_halo_launches = 0;  // vgpu_conv_halo_launches (tests: the halo path ran)
 int g_stem_band = 0;      // vgpu_stem_set_band: 0 = stem_plan.h's rule, k = bands of k pooled rows
+int g_conv23_halo = -1;   // vgpu_conv23_set_halo: -1 = env VGPU_CONV23_HALO, 0 = the ring, 1 = the halo form when eligible
+unsigned long long g_conv23_halo_launches = 0;  // vgpu_conv23_halo_launches (tests: the halo form ran)
 
 convplan::ConvKnobs conv_knobs() {
   const char* big = g_forced_big < 0 ? getenv("VGPU_CONV_BIG") : nullptr;
@@ -2201,12 +2342,19 @@ ConvKernel conv_kernel(const convplan::ConvPlan& p) {
 #undef VGPU_BN_RES
 #undef VGPU_TILES
 
-// conv23_kernel<BM, W, NEXT, 3, kThreads, POST, SC>, [W == 128][plain, next, post, next + sc]
+// conv23_kernel<BM, W, NEXT, 3, kThreads, POST, SC, HALO>, [HALO][W == 128][plain, next, post, next + sc];
+// the halo form exists for W = 64 only (conv_plan.h, conv23_halo_ok)
 using Conv23Kernel = void (*)(const ConvArgs, const ConvArgs, const ConvArgs);
-const Conv23Kernel kConv23[2][4] = {
-    {conv23_kernel<128, 64>, conv23_kernel<128, 64, true>, conv23_kernel<128, 64, false, 3, kThreads, true>,
-     conv23_kernel<128, 64, true, 3, kThreads, false, true>},
-    {conv23_kernel<64, 128>, conv23_kernel<64, 128, true>, conv23_kernel<64, 128, false, 3, kThreads, true>, nullptr}};
+#define VGPU_CONV23_64(halo)                                                                                    \
+  {conv23_kernel<128, 64, false, 3, kThreads, false, false, halo>,                                              \
+   conv23_kernel<128, 64, true, 3, kThreads, false, false, halo>,                                               \
+   conv23_kernel<128, 64, false, 3, kThreads, true, false, halo>,                                               \
+   conv23_kernel<128, 64, true, 3, kThreads, false, true, halo>}
+const Conv23Kernel kConv23[2][2][4] = {
+    {VGPU_CONV23_64(false),
+     {conv23_kernel<64, 128>, conv23_kernel<64, 128, true>, conv23_kernel<64, 128, false, 3, kThreads, true>, nullptr}},
+    {VGPU_CONV23_64(true), {nullptr, nullptr, nullptr, nullptr}}};
+#undef VGPU_CONV23_64
 
 // The one launcher: tile counts from the plan, the plan's kernel on the plan's
 // grid, and the split-K reduce behind it when the plan splits.
@@ -2673,6 +2821,9 @@ VGPU_API void vgpu_conv_set_halo(int mode) { g_forced_halo = mode; }  // -1 env,
 VGPU_API unsigned long long vgpu_conv_halo_launches() { return g_halo_launches; }
 // Test / A-B knob of the fused stem: pooled rows per band (0 = heuristic, 1 = one pooled row per band).
 VGPU_API void vgpu_stem_set_band(int rows) { g_stem_band = rows < 0 ? 0 : rows; }
+// conv23's halo form of phase 1: -1 env VGPU_CONV23_HALO, 0 off (the ring), 1 on when the shape is eligible.
+VGPU_API void vgpu_conv23_set_halo(int mode) { g_conv23_halo = mode; }
+VGPU_API unsigned long long vgpu_conv23_halo_launches() { return g_conv23_halo_launches; }
 
 namespace {
 // A vgpu_conv23* call: conv2 (a: x, w, bias, shape), conv3 (b: w, y, res; post: qscale / qshift; shortcut
@@ -2712,7 +2863,10 @@ int conv23_impl(const Conv23Args& r, hipStream_t s) {
   if (!bm || stride < 1 || N < 1 || !a.bias || !b.res || (sc && stride != 1)) return -1;
   if (next && (!cn.bias || !cn.pscale || !cn.pshift || !cn.y)) return -1;
   if ((b.qscale == nullptr) != (b.qshift == nullptr)) return -1;
-  const Conv23Kernel kern = kConv23[C == 128][sc ? 3 : next ? 1 : post ? 2 : 0];
+  const bool halo = (g_conv23_halo < 0 ? conv23_halo_enabled() : g_conv23_halo > 0) &&
+                    convplan::conv23_halo_ok(C, stride, W, bm);
+  const Conv23Kernel kern = kConv23[halo][C == 128][sc ? 3 : next ? 1 : post ? 2 : 0];
+  if (!kern) return -1;
   a.OH = (H + 2 - 3) / stride + 1;
   a.OW = (W + 2 - 3) / stride + 1;
   if (a.OH < 1 || a.OW < 1) return -1;
@@ -2746,6 +2900,7 @@ int conv23_impl(const Conv23Args& r, hipStream_t s) {
       e.y_bytes = (uint32_t)(nb * hi);
     }
     c.nM = (c.M + bm - 1) / bm; c.nN = 1; c.nwg = c.nM;
+    if (halo) ++g_conv23_halo_launches;
     hipLaunchKernelGGL(kern, dim3(c.nwg), dim3(kThreads), 0, s, c, d, e);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) return (int)err;

@@ -198,4 +198,29 @@ constexpr int conv23_bm(int C, bool next, bool post, bool sc) {
   return C == 64 ? 128 : 64;
 }
 
+// conv23's halo form of phase 1 (conv23_kernel<..., HALO>, stride 1): the region the
+// 3-stage ring of (A tile + weight panel) occupies holds, per 64-channel block, one
+// 128-B row per input pixel of the flat range [m0 − W − 1, m0 + BM + W + 1) that a
+// tile of BM consecutive output pixels reads -- BM + 2W + 2 rows, all nine taps read
+// their A fragments from it -- with the block's last row a zero row (padding taps
+// and rows past M), and behind the halo a ring of `conv23_halo_ring` weight panels
+// (C rows x 128 B).  Rows are DMA'd 32 at a time, so the row count is a multiple of 32.
+constexpr int conv23_region(int C, int bm) { return 3 * (bm + C) * 128; }  // the ring form's LDS region, bytes
+constexpr int conv23_halo_ring(int C) { return C == 64 ? 4 : 2; }          // weight panels in the halo form's ring
+constexpr int conv23_halo_rows(int C, int bm) {  // halo rows per 64-channel block, the zero row included
+  return (conv23_region(C, bm) - conv23_halo_ring(C) * C * 128) / 128 / (C / 64) / 32 * 32;
+}
+constexpr int conv23_halo_bytes(int C, int bm) {  // halo image + weight ring
+  return conv23_halo_rows(C, bm) * (C / 64) * 128 + conv23_halo_ring(C) * C * 128;
+}
+// Whether a W-wide image runs the halo form: stride 1, C = 64, and the tile's halo
+// rows plus the zero row fit (W ≤ 94: the flagship's 87 does).  Anything else keeps
+// the ring.  C = 128 is not taken: there the region leaves a ring of two 16 KB panels,
+// and on the flagship's 44-wide stage 2 the form gained 3-6 us per tail, inside the
+// ring form's own round-to-round spread (profiles/r11/tail_halo), so it was not kept.
+constexpr bool conv23_halo_ok(int C, int stride, int W, int bm) {
+  if (stride != 1 || C != 64 || W < 1 || bm < 1 || bm % 32) return false;
+  return (int64_t)bm + 2 * (int64_t)W + 3 <= conv23_halo_rows(C, bm);
+}
+
 }  // namespace convplan

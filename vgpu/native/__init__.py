@@ -109,6 +109,10 @@ def load_kernels() -> ctypes.CDLL:
     lib.vgpu_conv_set_big.argtypes = [ci]
     lib.vgpu_conv_set_halo.argtypes = [ci]
     lib.vgpu_conv_halo_launches.restype = ctypes.c_ulonglong
+    # the fused tails' halo form of phase 1: -1 env VGPU_CONV23_HALO, 0 the ring, 1 on when eligible
+    lib.vgpu_conv23_set_halo.argtypes = [ci]
+    lib.vgpu_conv23_set_halo.restype = None
+    lib.vgpu_conv23_halo_launches.restype = ctypes.c_ulonglong
     lib.vgpu_lstm_recurrence.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp]
     lib.vgpu_lstm_recurrence.restype = ci
     lib.vgpu_lstm_forward_train.argtypes = [vp] * 5 + [ci, ci, ci, vp]
