@@ -12,7 +12,14 @@ smoothing), for
 A target outside [0, C) or equal to ``ignore_index`` drops its row from the
 loss and the mean, as PyTorch's ``ignore_index`` does (the kernel
 used to give such a row loss 0 but still count it and give it a gradient).
-The training pods use it (PyTorch's path was eight small kernels per step)."""
+The training pods use it (PyTorch's path was eight small kernels per step).
+
+2-D logits may be a padded-row view (``stride(0) > C``, a [rows, C] cut from
+wider rows): the kernel reads them in place and writes the gradient at the same
+strides, so the gradient is allocated with those strides (``_grad_like``;
+``torch.empty_like`` would pack it to [rows, C] and the kernel would run past
+its end) and the backward returns it with them.  The pad columns are never
+read or written."""
 from __future__ import annotations
 
 import ctypes
@@ -38,7 +45,10 @@ def _lib():
 
 
 def _layout(x: torch.Tensor):
-    """(rows, C, hw, bstride, pstride, cstride) of 2-D or 4-D logits, or None."""
+    """(rows, C, hw, bstride, pstride, cstride) of 2-D or 4-D logits the kernel
+    reads in place, or None: 2-D with unit column stride and stride(0) >= C
+    (dense or padded rows), 4-D NCHW-contiguous or channels-last.  Every
+    element (row, c) of a tensor from ``_grad_like`` sits at the same offset."""
     if x.dim() == 2:
         rows, c = x.shape
         if x.stride(1) != 1 or x.stride(0) < c:
@@ -55,6 +65,13 @@ def _layout(x: torch.Tensor):
     return None
 
 
+def _grad_like(logits: torch.Tensor) -> torch.Tensor:
+    """Uninitialised dlogits whose storage has the logits' own strides.  For
+    the dense layouts this is what ``torch.empty_like`` gives; for a padded-row
+    view ``empty_like`` packs the rows, and the kernel addresses by stride."""
+    return torch.empty_strided(logits.shape, logits.stride(), dtype=logits.dtype, device=logits.device)
+
+
 class _CrossEntropyFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, target, ignore_index, lay):
@@ -63,7 +80,7 @@ class _CrossEntropyFn(torch.autograd.Function):
         loss_rows = torch.empty(lib.vgpu_cross_entropy_rows_workspace(rows, c), dtype=torch.float32,
                                 device=logits.device)
         out = torch.empty(2, dtype=torch.float32, device=logits.device)
-        dlogits = torch.empty_like(logits)  # same layout as the logits
+        dlogits = _grad_like(logits)  # same strides as the logits
         p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
         rc = lib.vgpu_cross_entropy_fwd_bwd2(p(logits), p(target), p(loss_rows), p(out), p(dlogits), rows, c,
                                                 int(ignore_index), hw, bs, ps, cs,
@@ -78,7 +95,10 @@ class _CrossEntropyFn(torch.autograd.Function):
     def backward(ctx, g):
         dlogits, out = ctx.saved_tensors
         # 0-dim scale: the multiply does not promote (one kernel, a bf16 result)
-        return dlogits * (g * out[1]), None, None, None
+        scale = g * out[1]
+        if dlogits.dim() == 2 and dlogits.stride(0) != dlogits.shape[1]:  # padded rows: keep the strides
+            return torch.mul(dlogits, scale, out=_grad_like(dlogits)), None, None, None
+        return dlogits * scale, None, None, None
 
 
 def cross_entropy(logits: torch.Tensor, target: torch.Tensor, ignore_index: int = -100) -> torch.Tensor:
