@@ -440,6 +440,121 @@ def part_r(tokens: int, ctx: int, windows: int, fp8: bool = False) -> dict:
     return out
 
 
+def part_g(tokens: int, ctx: int, windows: int, fp8: bool = False) -> dict:
+    """Resident native graph decode with the token chosen, no shim, B = 1: per
+    model (bf16; fp8 too with `fp8`) four series whose windows alternate in one
+    process: `open` (part R's loop: the captured step replayed on a fixed
+    token, a host pos.fill_ before every replay; every window of every series
+    runs positions 0 .. tokens - 1), `host` (the same graph with
+    torch.argmax + copy_ into the token buffer + pos.fill_ between replays),
+    `closed_greedy` and `closed_sample` (decode + vgpu.ops.select captured as
+    one graph, as Llama.generate_native captures it: nothing between replays;
+    sampling with top_k 50, top_p 0.9, T 1).  Also, event-timed over 200
+    back-to-back calls on the last logits: one select call (its two launches)
+    and one torch.argmax, in microseconds."""
+    import statistics
+
+    import torch
+    from vgpu.models.llama import LlamaConfig
+    from vgpu.ops import select as S
+    if tokens > ctx:
+        raise SystemExit(f"--tokens {tokens}: a window has to fit the context ({ctx})")
+    cfg = LlamaConfig.llama3_8b()
+    out = {"ctx": ctx, "window_tokens": tokens, "sample": {"top_k": 50, "top_p": 0.9, "temperature": 1.0}}
+    for name in ["bf16"] + (["fp8"] if fp8 else []):
+        d = GraphDecoder(cfg, ctx, 1, native=True, fp8=name == "fp8")
+        dev = d.tok.device
+        step = torch.zeros(1, dtype=torch.long, device=dev)
+        res = torch.zeros(1, tokens, dtype=torch.long, device=dev)
+        ws = torch.empty(S.workspace_bytes(1, cfg.vocab) // 4, dtype=torch.int32, device=dev)
+        u = torch.rand(tokens, 1, generator=torch.Generator().manual_seed(1)).to(dev)
+
+        def select(logits, sample):
+            lg = logits.view(1, cfg.vocab)
+            if sample:
+                S.sample(lg, ws, step, d.pos, d.tok, res, u, 1.0, 50, 0.9)
+            else:
+                S.greedy(lg, ws, step, d.pos, d.tok, res)
+
+        closed = {}
+        for sample in (False, True):
+            step.zero_()
+            d.pos.zero_()
+            s = torch.cuda.Stream()
+            s.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(s), torch.inference_mode():
+                select(d.m.decode_native(d.tok, d.kv, d.pos), sample)  # eager once: loads the kernels
+            torch.cuda.current_stream().wait_stream(s)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g), torch.inference_mode():
+                select(d.m.decode_native(d.tok, d.kv, d.pos), sample)
+            closed["closed_sample" if sample else "closed_greedy"] = g
+        torch.cuda.synchronize()
+
+        def window_host():
+            t0 = time.time()
+            for i in range(tokens):
+                d.pos.fill_(i)
+                d.g.replay()
+                d.tok.copy_(d.out.view(-1).argmax().view(1, 1))
+            torch.cuda.synchronize()
+            return round(tokens / (time.time() - t0), 2)
+
+        def window_closed(g):
+            step.zero_()
+            d.pos.zero_()
+            torch.cuda.synchronize()
+            t0 = time.time()
+            for _ in range(tokens):
+                g.replay()
+            torch.cuda.synchronize()
+            return round(tokens / (time.time() - t0), 2)
+
+        def window_open():
+            d.n = 0  # positions 0 .. tokens - 1 in every window, as in the other series
+            return d.window(tokens)
+
+        runs = {"open": window_open, "host": window_host,
+                **{k: (lambda g=g: window_closed(g)) for k, g in closed.items()}}
+        for fn in runs.values():
+            fn()  # warm
+        series = {k: [] for k in runs}
+        for _ in range(windows):
+            for k, fn in runs.items():
+                series[k].append(fn())
+        assert int(step) == tokens and int(d.pos) == tokens  # the closed loop did advance on the device
+        mres = {k: {"tok_s": v, "median": statistics.median(v), "min": min(v), "max": max(v)}
+                for k, v in series.items()}
+        mres["closed_tokens_head"] = res[0, :8].tolist()
+
+        def per_call_us(fn, n=200):
+            fn()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(n):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            return round(e0.elapsed_time(e1) * 1000 / n, 2)
+
+        def reset_then(fn):
+            step.zero_()  # keeps step inside [0, tokens): every call does the whole selection
+            fn()
+
+        logits = d.out
+        mres["per_call_us"] = {
+            "step_zero_alone": per_call_us(step.zero_),
+            "greedy_with_step_zero": per_call_us(lambda: reset_then(lambda: select(logits, False))),
+            "sample_with_step_zero": per_call_us(lambda: reset_then(lambda: select(logits, True))),
+            "torch_argmax": per_call_us(lambda: logits.view(-1).argmax()),
+        }
+        mres["weight_bytes"] = d.weight_bytes
+        out[name] = mres
+        del d, closed, runs, logits
+        torch.cuda.empty_cache()
+    return out
+
+
 def part_p(prompt: int, windows: int) -> dict:
     """Resident prompt processing, no shim, B = 1: the eager `forward(tokens,
     kv, 0)` against `prefill_native(tokens, kv, 0)` on one set of weights,
@@ -554,6 +669,9 @@ def main(argv=None) -> int:
                     help="resident graph decode, no shim: decode_static against decode_native, alternating windows")
     ap.add_argument("--part-p", action="store_true",
                     help="resident prompt processing, no shim: forward against prefill_native, alternating windows")
+    ap.add_argument("--part-g", action="store_true",
+                    help="resident native graph decode with the token chosen: open loop, host argmax loop, and the "
+                         "closed loop of generate_native's graph (greedy and top-k / top-p), alternating windows")
     ap.add_argument("--prompt", type=int, default=2048, help="prompt tokens of part P")
     ap.add_argument("--native-decode", action="store_true",
                     help="parts D and E capture Llama.decode_native (the project's kernels) instead of decode_static")
@@ -562,8 +680,8 @@ def main(argv=None) -> int:
     ap.add_argument("--skip-a", action="store_true")
     ap.add_argument("--skip-b", action="store_true")
     a = ap.parse_args(argv)
-    if a.fp8 and not (a.part_r or a.native_decode):
-        ap.error("--fp8 goes with --native-decode (parts D and E) or --part-r")
+    if a.fp8 and not (a.part_r or a.part_g or a.native_decode):
+        ap.error("--fp8 goes with --native-decode (parts D and E), --part-r or --part-g")
     if a.child_a:
         print("VMEM_A " + json.dumps(part_a_child(a.spill_gib)), flush=True)
         return 0
@@ -578,6 +696,9 @@ def main(argv=None) -> int:
         return 0
     if a.part_r:
         print("VMEM_R " + json.dumps(part_r(a.tokens, a.ctx, a.windows, a.fp8)), flush=True)
+        return 0
+    if a.part_g:
+        print("VMEM_G " + json.dumps(part_g(a.tokens, a.ctx, a.windows, a.fp8)), flush=True)
         return 0
     if a.part_p:
         print("VMEM_P " + json.dumps(part_p(a.prompt, a.windows)), flush=True)

@@ -189,6 +189,72 @@ def _prefill(cfg, x, norms, norm_f, rope, kv_caches, start, linear):
     return logits.view(B, 1, cfg.vocab)
 
 
+@torch.no_grad()
+def _generate(model, tokens, kv_caches, max_new, start, temperature, top_k, top_p, seed, eos, graph):
+    """The body of generate_native, shared by Llama and LlamaFp8: the model's
+    own prefill_native and decode_native with vgpu.ops.select after each."""
+    from vgpu.ops import select as S
+    cfg = model.cfg
+    if tokens.dim() != 2 or tokens.shape[1] < 1:
+        raise ValueError(f"tokens: shape {tuple(tokens.shape)}, expected [B, S] with S >= 1")
+    B, S_ = tokens.shape
+    greedy = temperature == 0
+    why = S.shape_reason(B, cfg.vocab, 1 if greedy else top_k)
+    if not why and not greedy:
+        why = S.params_reason(temperature, top_k, top_p)
+    if why:
+        raise ValueError(f"generate not supported: {why}")
+    if not isinstance(max_new, int) or max_new < 1:
+        raise ValueError(f"max_new: {max_new!r}, expected an integer >= 1")
+    if len(kv_caches) != cfg.layers or not cfg.layers or kv_caches[0][0].dim() != 4:
+        raise ValueError(f"kv_caches: expected {cfg.layers} layers of [B, KVH, ctx, hd] pairs")
+    limit = min(kv_caches[0][0].shape[2], cfg.max_seq)
+    if start < 0 or start + S_ + max_new - 1 > limit:
+        raise ValueError(f"start {start} + prompt {S_} + max_new {max_new} - 1 exceeds min(ctx, max_seq) = {limit}")
+    eos = -1 if eos is None else eos
+    if not isinstance(eos, int) or not -1 <= eos < cfg.vocab:
+        raise ValueError(f"eos: {eos!r}, expected None or a token id below {cfg.vocab}")
+    dev = tokens.device
+    out = torch.zeros(B, max_new, dtype=torch.int64, device=dev)
+    next_tok = torch.zeros(B, 1, dtype=torch.int64, device=dev)
+    step = torch.zeros(1, dtype=torch.int64, device=dev)
+    pos = torch.full((1,), start + S_ - 1, dtype=torch.int64, device=dev)
+    u = None
+    if not greedy:  # drawn on the CPU, copied once: a run is a function of its arguments
+        u = torch.rand(max_new, B, generator=torch.Generator().manual_seed(seed)).to(dev)
+
+    logits = model.prefill_native(tokens, kv_caches, start)
+    ws = torch.empty(S.workspace_bytes(B, cfg.vocab) // 4, dtype=torch.int32, device=dev)
+
+    def select(logits):
+        lg = logits.view(B, cfg.vocab)
+        if greedy:
+            S.greedy(lg, ws, step, pos, next_tok, out, eos)
+        else:
+            S.sample(lg, ws, step, pos, next_tok, out, u, temperature, top_k, top_p, eos)
+
+    def decode_select():
+        select(model.decode_native(next_tok, kv_caches, pos))
+
+    select(logits)  # pos: now the row the new token's k / v go to
+    left = max_new - 1
+    if graph and max_new > 2:
+        decode_select()  # eager: real work, and it loads every kernel
+        left -= 1
+        g = torch.cuda.CUDAGraph()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.graph(g, stream=side):  # a capture executes nothing: no state to restore
+            decode_select()
+        for _ in range(left):
+            g.replay()
+    else:
+        for _ in range(left):
+            decode_select()
+    torch.cuda.current_stream().synchronize()
+    return out
+
+
 class Llama(nn.Module):
     def __init__(self, cfg: LlamaConfig):
         super().__init__()
@@ -283,6 +349,27 @@ class Llama(nn.Module):
         return _prefill(self.cfg, self.embed(tokens), [(l.norm1.weight, l.norm2.weight) for l in self.layers],
                         self.norm.weight, self.rope(tokens.device), kv_caches, start, linear)
 
+    def generate_native(self, tokens: torch.Tensor, kv_caches, max_new: int, *, start: int = 0,
+                        temperature: float = 0.0, top_k: int = 1, top_p: float = 1.0, seed: int = 0, eos=None,
+                        graph: bool = True) -> torch.Tensor:
+        """`max_new` tokens after the prompt `tokens` [B, S] (int64), chosen on the
+        device: prefill_native, then decode_native max_new - 1 times, each followed
+        by vgpu.ops.select, which writes the token where the next embedding reads
+        it and advances `pos` there.  temperature 0: greedy (first index in
+        select's ordering); otherwise top-k (at most 64) / top-p sampling at that
+        temperature, with u = torch.rand(max_new, B, generator=torch.Generator()
+        .manual_seed(seed)) drawn on the CPU, so a run is reproducible from its
+        arguments.  top_p acts inside the top-k set only (no nucleus over the whole
+        vocabulary).  graph (and max_new > 2): the first decode + select runs
+        eagerly, the second is captured as one graph on a side stream and
+        replayed for the rest with no host work between replays.  One host
+        synchronisation, at the end.  With `eos` the loop still runs max_new steps:
+        a row that has emitted eos is padded with eos.  Needs max_new >= 1 and
+        start + S + max_new - 1 <= min(ctx, cfg.max_seq) (the last token chosen is
+        never fed back); otherwise, and for whatever prefill_native, decode_native
+        or select refuse, ValueError.  Returns int64 [B, max_new]."""
+        return _generate(self, tokens, kv_caches, max_new, start, temperature, top_k, top_p, seed, eos, graph)
+
     def new_kv_cache(self, batch: int, seq: int, dtype=torch.bfloat16, device=None):
         hd = self.cfg.dim // self.cfg.heads
         shape = (batch, self.cfg.kv_heads, seq, hd)
@@ -325,6 +412,7 @@ class LlamaFp8(nn.Module):
 
     rope = Llama.rope
     new_kv_cache = Llama.new_kv_cache
+    generate_native = Llama.generate_native  # over this class's prefill_native and decode_native
 
     @classmethod
     @torch.no_grad()
