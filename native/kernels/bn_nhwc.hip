@@ -27,11 +27,11 @@
 #include <math.h>
 #include <stdint.h>
 
-#define VGPU_API extern "C" __attribute__((visibility("default")))
+#include "act.h"
+#include "bf16.h"
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kUnroll = 4;           // rows in flight per thread (default; 8 via vgpu_bn_set_tuning)
 constexpr int kMaxChunk = 512;       // channels per reduction workgroup
 constexpr int kTargetBlocks = 1024;  // reduction grid ≈ 4 workgroups per CU (default)
@@ -47,40 +47,11 @@ struct alignas(16) bf16x8 {
   uint16_t v[8];
 };
 
-__device__ __forceinline__ float bf2f(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
-
-__device__ __forceinline__ uint16_t f2bf(float f) {
-  __bf16 b = (__bf16)f;
-  return __builtin_bit_cast(uint16_t, b);
-}
-
 // Parameter access: P = float or uint16_t (bf16 bits); a null pointer reads as dflt.
 __device__ __forceinline__ float ldp(const float* p, int i, float dflt) { return p ? p[i] : dflt; }
 __device__ __forceinline__ float ldp(const uint16_t* p, int i, float dflt) { return p ? bf2f(p[i]) : dflt; }
 __device__ __forceinline__ void stp(float* p, int i, float v) { p[i] = v; }
 __device__ __forceinline__ void stp(uint16_t* p, int i, float v) { p[i] = f2bf(v); }
-
-template <int kAct>
-__device__ __forceinline__ float act_fwd(float z) {
-  if constexpr (kAct == 1) return fmaxf(z, 0.0f);
-  if constexpr (kAct == 2) return fminf(fmaxf(z, 0.0f), 6.0f);
-  return z;
-}
-
-// d act / dz as PyTorch defines it (threshold_backward / hardtanh_backward).
-template <int kAct>
-__device__ __forceinline__ float act_grad(float z) {
-  if constexpr (kAct == 1) return z > 0.0f ? 1.0f : 0.0f;
-  if constexpr (kAct == 2) return (z > 0.0f && z < 6.0f) ? 1.0f : 0.0f;
-  return 1.0f;
-}
-
-__device__ __forceinline__ void load8(const float* __restrict__ p, float (&o)[8]) {
-  const float4 a = *reinterpret_cast<const float4*>(p);
-  const float4 b = *reinterpret_cast<const float4*>(p + 4);
-  o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w;
-  o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
-}
 
 // Per-channel reduction.  Grid (G, ceil(C / chunk)); a workgroup reduces
 // `rows_per_block` rows of one channel chunk into partial[blockIdx.x][c].
@@ -271,8 +242,8 @@ __global__ void __launch_bounds__(kThreads) bn_apply_kernel(const bf16x8* __rest
   VGPU_BN_GRID_LOOP(i, ci, nvec, cvec) {
     const bf16x8 v = x[i];
     float s[8], t[8];
-    load8(sc + ci * 8, s);
-    load8(sh + ci * 8, t);
+    load8f(sc + ci * 8, s);
+    load8f(sh + ci * 8, t);
     bf16x8 o;
 #pragma unroll
     for (int k = 0; k < 8; ++k) o.v[k] = f2bf(act_fwd<kAct>(fmaf(bf2f(v.v[k]), s[k], t[k])));
@@ -296,10 +267,10 @@ __global__ void __launch_bounds__(kThreads) bn_bwd_apply_kernel(const bf16x8* __
     bf16x8 r;
     if constexpr (kAdd) r = add[i];
     float s[8], t[8], cc[8], b[8];
-    load8(coef + ci * 8, s);
-    load8(coef + C + ci * 8, t);
-    load8(coef + 2 * C + ci * 8, cc);
-    load8(coef + 3 * C + ci * 8, b);
+    load8f(coef + ci * 8, s);
+    load8f(coef + C + ci * 8, t);
+    load8f(coef + 2 * C + ci * 8, cc);
+    load8f(coef + 3 * C + ci * 8, b);
     bf16x8 o;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {

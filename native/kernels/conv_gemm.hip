@@ -37,21 +37,17 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "act.h"
+#include "bf16.h"
 #include "conv_plan.h"
 #include "stem_plan.h"
-
-#define VGPU_API extern "C" __attribute__((visibility("default")))
 
 namespace {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-// Native 16-B vector (HIP's u32x4 is a class; copies of it go through memcpy
-// and defeat register promotion of the staging arrays).
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 
-constexpr int kThreads = 256;
 constexpr int BK = 64;
 
 struct ConvArgs {
@@ -108,39 +104,8 @@ struct ConvArgs {
   const float* qshift;
 };
 
-// d act / d z as PyTorch defines it (threshold_backward / hardtanh_backward).
-__device__ __forceinline__ float bn_act_grad(int act, float z) {
-  if (act == 1) return z > 0.0f ? 1.0f : 0.0f;
-  if (act == 2) return (z > 0.0f && z < 6.0f) ? 1.0f : 0.0f;
-  return 1.0f;
-}
-
 // Keep `v` in a VGPR as it is here (no rematerialisation, no hoisting past this point).
 __device__ __forceinline__ void pin_vgpr(uint32_t& v) { asm volatile("" : "+v"(v)); }
-
-__device__ __forceinline__ void unpack8(const u32x4 v, float (&f)[8]) {
-  f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
-  f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
-  f[4] = __uint_as_float(v.z << 16); f[5] = __uint_as_float(v.z & 0xffff0000u);
-  f[6] = __uint_as_float(v.w << 16); f[7] = __uint_as_float(v.w & 0xffff0000u);
-}
-typedef __attribute__((ext_vector_type(2))) float f32x2_t;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-// One v_cvt_pk_bf16_f32 per pair (RNE, the same rounding as two scalar
-// conversions); the scalar form costs two conversions + shift + or.
-__device__ __forceinline__ uint32_t pack2(float lo, float hi) {
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2_t{lo, hi}, bf16x2_t));
-}
-__device__ __forceinline__ u32x4 pack8(const float (&f)[8]) {
-  return u32x4{pack2(f[0], f[1]), pack2(f[2], f[3]), pack2(f[4], f[5]), pack2(f[6], f[7])};
-}
-
-__device__ __forceinline__ void load8f(const float* p, float (&o)[8]) {
-  const float4 b0 = *reinterpret_cast<const float4*>(p);
-  const float4 b1 = *reinterpret_cast<const float4*>(p + 4);
-  o[0] = b0.x; o[1] = b0.y; o[2] = b0.z; o[3] = b0.w;
-  o[4] = b1.x; o[5] = b1.y; o[6] = b1.z; o[7] = b1.w;
-}
 
 // The post epilogue on 8 stored (bf16) values: relu(y·s + t) rounded to bf16, the
 // same expression as conv_pro_kernel's store_a and tail_epilogue's NEXT branch
@@ -157,10 +122,7 @@ __device__ __forceinline__ void load_bias8(const ConvArgs& a, int col, float (&b
   if (a.bias_bf16) {
     unpack8(*reinterpret_cast<const u32x4*>(reinterpret_cast<const uint16_t*>(a.bias) + col), bb);
   } else {
-    const float4 b0 = *reinterpret_cast<const float4*>(a.bias + col);
-    const float4 b1 = *reinterpret_cast<const float4*>(a.bias + col + 4);
-    bb[0] = b0.x; bb[1] = b0.y; bb[2] = b0.z; bb[3] = b0.w;
-    bb[4] = b1.x; bb[5] = b1.y; bb[6] = b1.z; bb[7] = b1.w;
+    load8f(a.bias + col, bb);
   }
 }
 
@@ -636,7 +598,7 @@ __device__ __forceinline__ void epilogue_halves(const ConvArgs& a,
       if constexpr (bwd) {
         unpack8(xb[h][i], xf);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] *= bn_act_grad(a.bnact, fmaf(xf[j], bs[j], bt[j]));
+        for (int j = 0; j < 8; ++j) v[j] *= act_grad(a.bnact, fmaf(xf[j], bs[j], bt[j]));
       }
       u32x4 o = pack8(v);
       if constexpr (POST) o = post_act8(o, qs, qt);
@@ -1397,7 +1359,7 @@ __global__ void __launch_bounds__(BM * BN / 64, 2) conv_halo_kernel(const ConvAr
       if constexpr (ST == 2) {
         unpack8(xb[r], xf);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] *= bn_act_grad(a.bnact, fmaf(xf[j], ks_[j], kt_[j]));
+        for (int j = 0; j < 8; ++j) v[j] *= act_grad(a.bnact, fmaf(xf[j], ks_[j], kt_[j]));
       }
       const u32x4 o = pack8(v);
       if (m < a.M) *reinterpret_cast<u32x4*>(a.y + (int64_t)m * a.Cout + col) = o;

@@ -27,18 +27,16 @@
 #include <stdint.h>
 #include <stdlib.h>
 
-#define VGPU_API extern "C" __attribute__((visibility("default")))
+#include "bf16.h"
 
 namespace {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 typedef __attribute__((address_space(3))) char lds_char;  // 32-bit LDS addressing
 
-constexpr int kThreads = 256;
 constexpr int KP = 32;                     // pixels per K step (one MFMA depth)
 constexpr uint32_t kOOB = 0x80000000u;     // buffer offset past num_records: loads return 0
 typedef __attribute__((address_space(3))) void lds_void_t;
@@ -55,11 +53,6 @@ struct WgradArgs {
   int nseg;            // 3x3 tap-fused path: 32-pixel segments per output row
   uint32_t dy_bytes, x_bytes;
 };
-
-__device__ __forceinline__ uint16_t f2bf(float f) {
-  __bf16 b = (__bf16)f;
-  return __builtin_bit_cast(uint16_t, b);
-}
 
 // LDS images of [pixel][channel] tiles are XOR-swizzled by 32-B column group:
 // a 32-lane half of a transposed read covers pixel rows {8g+q, 8g+8+q} (q<4)

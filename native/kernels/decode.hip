@@ -19,41 +19,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define VGPU_API extern "C" __attribute__((visibility("default")))
+#include "bf16.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-
-__device__ __forceinline__ void unpack8(const u32x4 v, float (&f)[8]) {
-  f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
-  f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
-  f[4] = __uint_as_float(v.z << 16); f[5] = __uint_as_float(v.z & 0xffff0000u);
-  f[6] = __uint_as_float(v.w << 16); f[7] = __uint_as_float(v.w & 0xffff0000u);
-}
-__device__ __forceinline__ uint32_t pack2(float a, float b) {
-  typedef __attribute__((ext_vector_type(2))) float f2;
-  typedef __attribute__((ext_vector_type(2))) __bf16 b2;
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f2{a, b}, b2));
-}
-__device__ __forceinline__ u32x4 pack8(const float (&f)[8]) {
-  return u32x4{pack2(f[0], f[1]), pack2(f[2], f[3]), pack2(f[4], f[5]), pack2(f[6], f[7])};
-}
-__device__ __forceinline__ void load8f(const float* p, float (&f)[8]) {
-  const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
-  f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w;
-  f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
-}
-__device__ __forceinline__ void store8f(float* p, const float (&f)[8]) {
-  reinterpret_cast<float4*>(p)[0] = float4{f[0], f[1], f[2], f[3]};
-  reinterpret_cast<float4*>(p)[1] = float4{f[4], f[5], f[6], f[7]};
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 // exp(a - b) for softmax maxima: 0 when a is the empty maximum (-inf), also
 // when b is (-inf - -inf would be NaN).
 __device__ __forceinline__ float exp_diff(float a, float b) { return a == -INFINITY ? 0.0f : __expf(a - b); }

@@ -28,37 +28,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define VGPU_API extern "C" __attribute__((visibility("default")))
+#include "bf16.h"
 
 namespace {
-
-constexpr int kThreads = 256;
-
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-
-__device__ __forceinline__ void unpack8(const u32x4 v, float (&f)[8]) {
-  f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
-  f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
-  f[4] = __uint_as_float(v.z << 16); f[5] = __uint_as_float(v.z & 0xffff0000u);
-  f[6] = __uint_as_float(v.w << 16); f[7] = __uint_as_float(v.w & 0xffff0000u);
-}
-
-__device__ __forceinline__ uint32_t pack2(float lo, float hi) {
-  typedef __attribute__((ext_vector_type(2))) float f2;
-  typedef __attribute__((ext_vector_type(2))) __bf16 b2;
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f2{lo, hi}, b2));
-}
-
-__device__ __forceinline__ u32x4 pack8(const float (&v)[8]) {
-  return u32x4{pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7])};
-}
-
-__device__ __forceinline__ void load_w8(const float* __restrict__ w, int C, int tap, int c8, float (&f)[8]) {
-  const float4 a = *reinterpret_cast<const float4*>(w + (int64_t)tap * C + c8);
-  const float4 b = *reinterpret_cast<const float4*>(w + (int64_t)tap * C + c8 + 4);
-  f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w;
-  f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
-}
 
 // A thread's 8 channels x 9 taps of a bf16 [C][9] filter (w + c8 * 9: 144-B
 // aligned, since c8 is a multiple of 8).
@@ -86,7 +58,7 @@ __device__ __forceinline__ void tap_w8(const void* __restrict__ w, const W72& wc
 #pragma unroll
     for (int j = 0; j < 8; ++j) f[j] = wc.at(j, tap);
   } else {
-    load_w8(static_cast<const float*>(w), C, tap, c8, f);
+    load8f(static_cast<const float*>(w) + (int64_t)tap * C + c8, f);
   }
 }
 
@@ -285,8 +257,7 @@ __global__ void __launch_bounds__(kThreads) dw_wgrad_reduce_kernel(const float* 
     for (int r = 0; r < 16; ++r) a += red[r][el];
     if (c9) {
       const int C = n9c / 9, k = i / C, c = i - k * C;
-      __bf16 b = (__bf16)a;
-      static_cast<uint16_t*>(dw)[c * 9 + k] = __builtin_bit_cast(uint16_t, b);
+      static_cast<uint16_t*>(dw)[c * 9 + k] = f2bf(a);
     } else {
       static_cast<float*>(dw)[i] = a;
     }
@@ -386,8 +357,7 @@ __global__ void __launch_bounds__(kThreads) dw_wgrad2_kernel(const u32x4* __rest
     if (part) {
       part[(int64_t)blockIdx.y * 9 * s.C + (int64_t)k * s.C + c] = v;
     } else if (out_fmt) {
-      __bf16 b = (__bf16)v;
-      static_cast<uint16_t*>(out)[c * 9 + k] = __builtin_bit_cast(uint16_t, b);
+      static_cast<uint16_t*>(out)[c * 9 + k] = f2bf(v);
     } else {
       static_cast<float*>(out)[k * s.C + c] = v;
     }

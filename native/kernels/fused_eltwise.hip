@@ -18,38 +18,16 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define VGPU_API extern "C" __attribute__((visibility("default")))
+#include "act.h"
+#include "bf16.h"
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kMaxGrid = 256 * 8;
 
 struct alignas(16) bf16x8 {
   uint16_t v[8];
 };
-
-__device__ __forceinline__ float bf2f(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
-
-__device__ __forceinline__ uint16_t f2bf(float f) {
-  // v_cvt_pk_bf16_f32 on gfx950 (round-to-nearest-even, NaN-preserving)
-  __bf16 b = (__bf16)f;
-  return __builtin_bit_cast(uint16_t, b);
-}
-
-template <int kAct>
-__device__ __forceinline__ float act(float x) {
-  if constexpr (kAct == 1) return fmaxf(x, 0.0f);
-  if constexpr (kAct == 2) return fminf(fmaxf(x, 0.0f), 6.0f);
-  return x;
-}
-
-__device__ __forceinline__ void load8(const float* __restrict__ p, float (&o)[8]) {
-  const float4 a = *reinterpret_cast<const float4*>(p);
-  const float4 b = *reinterpret_cast<const float4*>(p + 4);
-  o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w;
-  o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
-}
 
 // Channel-group index tracked incrementally: one 64-bit modulo per thread,
 // then a compare-and-subtract per grid-stride step.
@@ -67,9 +45,9 @@ __global__ void __launch_bounds__(kThreads) bias_act_kernel(bf16x8* __restrict__
   VGPU_GRID_LOOP(i, ci, nvec, cvec) {
     bf16x8 v = x[i];
     float bb[8];
-    load8(bias + ci * 8, bb);
+    load8f(bias + ci * 8, bb);
 #pragma unroll
-    for (int k = 0; k < 8; ++k) v.v[k] = f2bf(act<kAct>(bf2f(v.v[k]) + bb[k]));
+    for (int k = 0; k < 8; ++k) v.v[k] = f2bf(act_fwd<kAct>(bf2f(v.v[k]) + bb[k]));
     x[i] = v;
   }
 }
@@ -81,11 +59,11 @@ __global__ void __launch_bounds__(kThreads) scale_shift_act_kernel(
   VGPU_GRID_LOOP(i, ci, nvec, cvec) {
     const bf16x8 v = x[i];
     float sc[8], sh[8];
-    load8(scale + ci * 8, sc);
-    load8(shift + ci * 8, sh);
+    load8f(scale + ci * 8, sc);
+    load8f(shift + ci * 8, sh);
     bf16x8 o;
 #pragma unroll
-    for (int k = 0; k < 8; ++k) o.v[k] = f2bf(act<kAct>(bf2f(v.v[k]) * sc[k] + sh[k]));
+    for (int k = 0; k < 8; ++k) o.v[k] = f2bf(act_fwd<kAct>(bf2f(v.v[k]) * sc[k] + sh[k]));
     y[i] = o;
   }
 }
@@ -99,8 +77,8 @@ __global__ void __launch_bounds__(kThreads) add_scale_shift_act_kernel(
     const bf16x8 va = a[i];
     const bf16x8 vb = b[i];
     float sc[8], sh[8];
-    load8(scale + ci * 8, sc);
-    load8(shift + ci * 8, sh);
+    load8f(scale + ci * 8, sc);
+    load8f(shift + ci * 8, sh);
     bf16x8 s, o;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
@@ -108,7 +86,7 @@ __global__ void __launch_bounds__(kThreads) add_scale_shift_act_kernel(
       // the activation from the rounded value (what an unfused graph computes)
       const uint16_t sk = f2bf(bf2f(va.v[k]) + bf2f(vb.v[k]));
       s.v[k] = sk;
-      o.v[k] = f2bf(act<kAct>(bf2f(sk) * sc[k] + sh[k]));
+      o.v[k] = f2bf(act_fwd<kAct>(bf2f(sk) * sc[k] + sh[k]));
     }
     s_out[i] = s;
     y[i] = o;

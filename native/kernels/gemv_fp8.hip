@@ -24,21 +24,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define VGPU_API extern "C" __attribute__((visibility("default")))
+#include "bf16.h"
 
 namespace {
 
-constexpr int kThreads = 256, kWaves = kThreads / 64;
+constexpr int kWaves = kThreads / 64;
 constexpr int kChunk = 16;  // weights per 16-byte load
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 
-__device__ __forceinline__ void unpack8(const u32x4 v, float* f) {
-  f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
-  f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
-  f[4] = __uint_as_float(v.z << 16); f[5] = __uint_as_float(v.z & 0xffff0000u);
-  f[6] = __uint_as_float(v.w << 16); f[7] = __uint_as_float(v.w & 0xffff0000u);
-}
 // 16 e4m3 codes (memory order) -> 16 floats: two packed converts per 32-bit word
 __device__ __forceinline__ void decode16(const u32x4 v, float (&f)[16]) {
   const uint32_t w[4] = {v.x, v.y, v.z, v.w};
@@ -48,19 +41,6 @@ __device__ __forceinline__ void decode16(const u32x4 v, float (&f)[16]) {
     const f32x2 hi = __builtin_amdgcn_cvt_pk_f32_fp8(w[i], true);
     f[4 * i + 0] = lo.x; f[4 * i + 1] = lo.y; f[4 * i + 2] = hi.x; f[4 * i + 3] = hi.y;
   }
-}
-__device__ __forceinline__ uint16_t f2bf(float f) {
-  __bf16 b = (__bf16)f;
-  return __builtin_bit_cast(uint16_t, b);
-}
-__device__ __forceinline__ uint32_t pack2(float a, float b) {
-  typedef __attribute__((ext_vector_type(2))) __bf16 b2;
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{a, b}, b2));
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 // Rows per block and chunks in flight per lane.  One trip of the K loop covers

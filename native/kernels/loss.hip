@@ -24,18 +24,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define VGPU_API extern "C" __attribute__((visibility("default")))
+#include "bf16.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-
-__device__ __forceinline__ float ld(const uint16_t* p, int64_t i) { return __uint_as_float((uint32_t)p[i] << 16); }
+__device__ __forceinline__ float ld(const uint16_t* p, int64_t i) { return bf2f(p[i]); }
 __device__ __forceinline__ float ld(const float* p, int64_t i) { return p[i]; }
-__device__ __forceinline__ void st(uint16_t* p, int64_t i, float v) {
-  __bf16 b = (__bf16)v;
-  p[i] = __builtin_bit_cast(uint16_t, b);
-}
+__device__ __forceinline__ void st(uint16_t* p, int64_t i, float v) { p[i] = f2bf(v); }
 __device__ __forceinline__ void st(float* p, int64_t i, float v) { p[i] = v; }
 
 struct Layout {

@@ -32,24 +32,18 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define VGPU_API extern "C" __attribute__((visibility("default")))
+#include "bf16.h"
 
 namespace {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 
 constexpr int kH = 128;            // hidden size (one wave's gate block)
 constexpr int kRows = 16;          // batch rows per workgroup
 constexpr int kHStride = kH + 8;   // h rows in LDS: 272 B (bank spread)
 constexpr int kPhases = 5;         // profiled phases of a forward step
 
-__device__ __forceinline__ float bf2f(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
-__device__ __forceinline__ uint16_t f2bf(float f) {
-  __bf16 b = (__bf16)f;
-  return __builtin_bit_cast(uint16_t, b);
-}
 // v_exp_f32 + v_rcp_f32 (1 ulp): an IEEE division here is a ~10-instruction
 // div_scale / div_fmas / div_fixup sequence, and a step evaluates 40 of these
 // per lane on the recurrence's critical path.  Saturates correctly: exp -> inf

@@ -15,17 +15,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define VGPU_API extern "C" __attribute__((visibility("default")))
+#include "bf16.h"
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kVec = 8;                      // bf16 per 16-B access
 constexpr int kIters = 4;                    // accesses per thread per block
 constexpr int kChunk = kThreads * kVec * kIters;  // 8192 elements per block
 constexpr int kMaxSeg = 48;
-
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 
 struct SgdSegs {
   uint16_t* p[kMaxSeg];
@@ -38,11 +35,6 @@ struct SgdSegs {
 
 __device__ __forceinline__ float lo(uint32_t v) { return __uint_as_float(v << 16); }
 __device__ __forceinline__ float hi(uint32_t v) { return __uint_as_float(v & 0xffff0000u); }
-__device__ __forceinline__ uint32_t pack2(float a, float b) {
-  typedef __attribute__((ext_vector_type(2))) float f2;
-  typedef __attribute__((ext_vector_type(2))) __bf16 b2;
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f2{a, b}, b2));
-}
 
 template <bool FIRST, bool NESTEROV>
 __device__ __forceinline__ void step2(uint32_t pv, uint32_t gv, uint32_t mv, float lr, float mom, float damp1,

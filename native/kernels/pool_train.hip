@@ -12,27 +12,11 @@
 #include <math.h>
 #include <stdint.h>
 
-#define VGPU_API extern "C" __attribute__((visibility("default")))
+#include "bf16.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
-
-__device__ __forceinline__ void unpack8(const u32x4 v, float (&f)[8]) {
-  f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
-  f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
-  f[4] = __uint_as_float(v.z << 16); f[5] = __uint_as_float(v.z & 0xffff0000u);
-  f[6] = __uint_as_float(v.w << 16); f[7] = __uint_as_float(v.w & 0xffff0000u);
-}
-
-__device__ __forceinline__ uint32_t pack2(float lo, float hi) {
-  typedef __attribute__((ext_vector_type(2))) float f2;
-  typedef __attribute__((ext_vector_type(2))) __bf16 b2;
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f2{lo, hi}, b2));
-}
 
 // One thread per (output pixel, 8 channels); grid-stride over N·OH·OW·C/8.
 // nchw: y is written [N][C][OH][OW] (the layout a following flatten reads
@@ -80,10 +64,7 @@ __global__ void __launch_bounds__(kThreads) maxpool_fwd_idx_kernel(const u32x4* 
       uint16_t* yh = reinterpret_cast<uint16_t*>(y);
       const int64_t hw = (int64_t)OH * OW, base = ((int64_t)n * cv * 8 + c * 8) * hw + (int64_t)oh * OW + ow;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        __bf16 b = (__bf16)m[j];
-        yh[base + j * hw] = __builtin_bit_cast(uint16_t, b);
-      }
+      for (int j = 0; j < 8; ++j) yh[base + j * hw] = f2bf(m[j]);
     } else {
       y[i] = u32x4{pack2(m[0], m[1]), pack2(m[2], m[3]), pack2(m[4], m[5]), pack2(m[6], m[7])};
     }
@@ -127,7 +108,7 @@ __global__ void __launch_bounds__(kThreads) maxpool_bwd_kernel(const u32x4* __re
           if (tj == tap) acc[j] += g[j];
         }
       }
-    dx[i] = u32x4{pack2(acc[0], acc[1]), pack2(acc[2], acc[3]), pack2(acc[4], acc[5]), pack2(acc[6], acc[7])};
+    dx[i] = pack8(acc);
   }
 }
 

@@ -14,17 +14,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define VGPU_API extern "C" __attribute__((visibility("default")))
+#include "bf16.h"
 
 namespace {
-
-constexpr int kThreads = 256;
-
-__device__ __forceinline__ float bf(uint16_t v) { return __uint_as_float((uint32_t)v << 16); }
-__device__ __forceinline__ uint16_t tobf(float f) {
-  __bf16 b = (__bf16)f;
-  return __builtin_bit_cast(uint16_t, b);
-}
 
 struct Src {
   int i0, i1;
@@ -62,7 +54,6 @@ __global__ void __launch_bounds__(kThreads) resize_kernel(const uint16_t* __rest
   const uint16_t* x11 = xn + ((int64_t)h.i1 * IW + w.i1) * C;
   uint16_t* out = y + p * C;
   if constexpr (kVec) {
-    typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
     for (int c = 0; c < C; c += 8) {
       const u32x4 a = *reinterpret_cast<const u32x4*>(x00 + c), b = *reinterpret_cast<const u32x4*>(x01 + c);
       const u32x4 d = *reinterpret_cast<const u32x4*>(x10 + c), e = *reinterpret_cast<const u32x4*>(x11 + c);
@@ -74,12 +65,14 @@ __global__ void __launch_bounds__(kThreads) resize_kernel(const uint16_t* __rest
       uint16_t* po = reinterpret_cast<uint16_t*>(&o);
 #pragma unroll
       for (int k = 0; k < 8; ++k)
-        po[k] = tobf(h.l0 * (w.l0 * bf(pa[k]) + w.l1 * bf(pb[k])) + h.l1 * (w.l0 * bf(pd[k]) + w.l1 * bf(pe[k])));
+        po[k] = f2bf(h.l0 * (w.l0 * bf2f(pa[k]) + w.l1 * bf2f(pb[k])) +
+                     h.l1 * (w.l0 * bf2f(pd[k]) + w.l1 * bf2f(pe[k])));
       *reinterpret_cast<u32x4*>(out + c) = o;
     }
   } else {
     for (int c = 0; c < C; ++c)
-      out[c] = tobf(h.l0 * (w.l0 * bf(x00[c]) + w.l1 * bf(x01[c])) + h.l1 * (w.l0 * bf(x10[c]) + w.l1 * bf(x11[c])));
+      out[c] = f2bf(h.l0 * (w.l0 * bf2f(x00[c]) + w.l1 * bf2f(x01[c])) +
+                    h.l1 * (w.l0 * bf2f(x10[c]) + w.l1 * bf2f(x11[c])));
   }
 }
 

@@ -47,16 +47,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define VGPU_API extern "C" __attribute__((visibility("default")))
+#include "bf16.h"
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kChunk = kThreads * 8;  // logits per block of a partial launch: one 16-B load per thread
 constexpr int kMaxTopK = 64;
 constexpr int kStage = 4096;  // candidates a row's final select holds in LDS: 64 chunks of 64 (V <= 131 072)
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 
 __device__ __forceinline__ uint32_t order_key(uint32_t bits) {
   bits &= 0xffffu;

@@ -15,41 +15,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define VGPU_API extern "C" __attribute__((visibility("default")))
+#include "act.h"
+#include "bf16.h"
 
 namespace {
-
-constexpr int kThreads = 256;
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-
-__device__ __forceinline__ void unpack8(const u32x4 v, float (&f)[8]) {
-  f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
-  f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
-  f[4] = __uint_as_float(v.z << 16); f[5] = __uint_as_float(v.z & 0xffff0000u);
-  f[6] = __uint_as_float(v.w << 16); f[7] = __uint_as_float(v.w & 0xffff0000u);
-}
-__device__ __forceinline__ float bf2f(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
-__device__ __forceinline__ uint16_t f2bf(float f) {
-  __bf16 b = (__bf16)f;
-  return __builtin_bit_cast(uint16_t, b);
-}
-__device__ __forceinline__ uint32_t pack2(float a, float b) {
-  typedef __attribute__((ext_vector_type(2))) float f2;
-  typedef __attribute__((ext_vector_type(2))) __bf16 b2;
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f2{a, b}, b2));
-}
-__device__ __forceinline__ float act_f(int act, float v) {
-  return act == 1 ? fmaxf(v, 0.0f) : act == 2 ? fminf(fmaxf(v, 0.0f), 6.0f) : v;
-}
-// d act / d z from the stored output y (relu: y > 0; relu6: 0 < y < 6)
-__device__ __forceinline__ float act_grad(int act, float y) {
-  return act == 1 ? (y > 0.0f ? 1.0f : 0.0f) : act == 2 ? ((y > 0.0f && y < 6.0f) ? 1.0f : 0.0f) : 1.0f;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // ---- forward: a block per R = 4 output rows, its 4 waves splitting K ---------------
 // Each wave streams every 4th 512-column chunk of the R rows (U = 4 chunks'
@@ -118,7 +87,7 @@ __global__ void __launch_bounds__(kThreads) skinny_fwd_kernel(const uint16_t* __
 #pragma unroll
     for (int q = 0; q < kFwdWaves; ++q) v += part[q][threadIdx.x];  // fixed order
     if (bias) v += bf2f(bias[n0 + r]);
-    y[(int64_t)b * N + n0 + r] = f2bf(act_f(act, v));
+    y[(int64_t)b * N + n0 + r] = f2bf(act_fwd(act, v));
   }
 }
 
@@ -238,12 +207,8 @@ __global__ void __launch_bounds__(kThreads) skinny_dgrad_kernel(const uint16_t* 
             sgd_elem(sj, bf2f(f2bf(o)), wf[j], mf[j]);  // the gradient as bf16, as unfused
           }
           const int64_t at = c + (int64_t)(nb + r + u) * kv;
-          __builtin_nontemporal_store(
-              u32x4{pack2(wf[0], wf[1]), pack2(wf[2], wf[3]), pack2(wf[4], wf[5]), pack2(wf[6], wf[7])},
-              reinterpret_cast<u32x4*>(sj.p) + at);
-          __builtin_nontemporal_store(
-              u32x4{pack2(mf[0], mf[1]), pack2(mf[2], mf[3]), pack2(mf[4], mf[5]), pack2(mf[6], mf[7])},
-              reinterpret_cast<u32x4*>(sj.m) + at);
+          __builtin_nontemporal_store(pack8(wf), reinterpret_cast<u32x4*>(sj.p) + at);
+          __builtin_nontemporal_store(pack8(mf), reinterpret_cast<u32x4*>(sj.m) + at);
         }
       }
     }
@@ -368,8 +333,7 @@ __global__ void __launch_bounds__(kThreads) skinny_wgrad_kernel(const uint16_t* 
     }
     // nontemporal: dW (205 MB for fc1) would otherwise push W out of the MALL
     // between this layer's data gradient and the optimizer
-    __builtin_nontemporal_store(u32x4{pack2(o[0], o[1]), pack2(o[2], o[3]), pack2(o[4], o[5]), pack2(o[6], o[7])},
-                                &reinterpret_cast<u32x4*>(dw)[(int64_t)(n0 + r) * kv + c]);
+    __builtin_nontemporal_store(pack8(o), &reinterpret_cast<u32x4*>(dw)[(int64_t)(n0 + r) * kv + c]);
   }
 }
 

@@ -23,11 +23,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define VGPU_API extern "C" __attribute__((visibility("default")))
+#include "bf16.h"
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kMaxGrid = 256 * 8;
 
 __device__ __forceinline__ uint32_t read_xcc_id() {

@@ -15,7 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define VGPU_API extern "C" __attribute__((visibility("default")))
+#include "bf16.h"
 
 namespace {
 

@@ -270,6 +270,13 @@ class Llama(nn.Module):
             self._rope = rope_tables(self.cfg, device)
         return self._rope
 
+    def _linear(self, name, i) -> nn.Linear:
+        """Projection `name` (one of LINEARS) of layer i, or the head (i None)."""
+        if name == "head":
+            return self.head
+        layer = self.layers[i]
+        return getattr(layer.attn if name in ("wqkv", "wo") else layer, name)
+
     def forward(self, tokens: torch.Tensor, kv_caches=None, pos: int = 0) -> torch.Tensor:
         cos, sin = self.rope(tokens.device)
         x = self.embed(tokens)
@@ -315,11 +322,10 @@ class Llama(nn.Module):
         contiguous bf16 caches on the GPU, batch 1-4 or 8, head_dim 64 or 128;
         anything else raises ValueError."""
         from vgpu.ops import decode as D
-        D.check_llama_decode(self, tokens, kv_caches, pos)
-        lin = [(l.attn.wqkv.weight, l.attn.wo.weight, l.w13.weight, l.w2.weight) for l in self.layers]
+        D.check_llama(self, tokens, kv_caches, pos, prefill=False, fp8=False)
 
         def linear(name, i, x, y):
-            D.gemv(x, self.head.weight if name == "head" else lin[i][LINEARS.index(name)], y)
+            D.gemv(x, self._linear(name, i).weight, y)
 
         return _decode_step(self.cfg, self.embed(tokens), [(l.norm1.weight, l.norm2.weight) for l in self.layers],
                             self.norm.weight, self.rope(tokens.device), kv_caches, pos, linear)
@@ -337,14 +343,12 @@ class Llama(nn.Module):
         anything else raises ValueError.  Returns the last token's logits
         [B, 1, vocab]."""
         from vgpu.ops import decode as D, prefill as P
-        P.check_llama_prefill(self, tokens, kv_caches, start)
-        lin = [(l.attn.wqkv.weight, l.attn.wo.weight, l.w13.weight, l.w2.weight) for l in self.layers]
+        D.check_llama(self, tokens, kv_caches, start, prefill=True, fp8=False)
 
         def linear(name, i, x, y):
-            if name == "head":  # B rows: the GEMV where it takes the batch
-                (D.gemv if x.shape[0] in D.BATCHES else P.gemm)(x, self.head.weight, y)
-            else:
-                P.gemm(x, lin[i][LINEARS.index(name)], y)
+            # the head has B rows: the GEMV where it takes the batch
+            gemv = name == "head" and x.shape[0] in D.BATCHES
+            (D.gemv if gemv else P.gemm)(x, self._linear(name, i).weight, y)
 
         return _prefill(self.cfg, self.embed(tokens), [(l.norm1.weight, l.norm2.weight) for l in self.layers],
                         self.norm.weight, self.rope(tokens.device), kv_caches, start, linear)
@@ -438,9 +442,8 @@ class LlamaFp8(nn.Module):
 
         layers = []
         for i, l in enumerate(model.layers):
-            mods = {"wqkv": l.attn.wqkv, "wo": l.attn.wo, "w13": l.w13, "w2": l.w2}
             layers.append(Fp8Block(keep(l.norm1.weight), keep(l.norm2.weight),
-                                   **{n: lin(m, f"layers.{i}.{n}") for n, m in mods.items()}))
+                                   **{n: lin(model._linear(n, i), f"layers.{i}.{n}") for n in LINEARS}))
         return cls(model.cfg, keep(model.embed.weight), layers, keep(model.norm.weight), lin(model.head, "head")).eval()
 
     @torch.no_grad()
@@ -452,13 +455,12 @@ class LlamaFp8(nn.Module):
         m = m.to(torch.bfloat16).to_empty(device=self.embed.device)
         m.embed.weight.copy_(self.embed)
         m.norm.weight.copy_(self.norm)
-        m.head.weight.copy_(Q.dequantize_ref(self.head.codes, self.head.scale))
         for src, dst in zip(self.layers, m.layers):
             dst.norm1.weight.copy_(src.norm1)
             dst.norm2.weight.copy_(src.norm2)
-            for name, lin in (("wqkv", dst.attn.wqkv), ("wo", dst.attn.wo), ("w13", dst.w13), ("w2", dst.w2)):
-                q = getattr(src, name)
-                lin.weight.copy_(Q.dequantize_ref(q.codes, q.scale))
+        for name, i in [("head", None)] + [(name, i) for i in range(self.cfg.layers) for name in LINEARS]:
+            q = self._linear(name, i)
+            m._linear(name, i).weight.copy_(Q.dequantize_ref(q.codes, q.scale))
         return m.eval()
 
     def _linear(self, name, i) -> Fp8Linear:
@@ -472,8 +474,8 @@ class LlamaFp8(nn.Module):
         """Llama.decode_native with the fp8 GEMV (vgpu.ops.fp8.gemv_fp8) in place
         of the bf16 one: the same ten dispatches per layer, the same caches,
         `pos` read on the device (graph-capturable)."""
-        from vgpu.ops import fp8 as Q
-        Q.check_llama_fp8_decode(self, tokens, kv_caches, pos)
+        from vgpu.ops import decode as D, fp8 as Q
+        D.check_llama(self, tokens, kv_caches, pos, prefill=False, fp8=True)
 
         def linear(name, i, x, y):
             q = self._linear(name, i)
@@ -491,10 +493,10 @@ class LlamaFp8(nn.Module):
         .prefill_native` bit for bit.  The head takes the fp8 GEMV where that
         takes the batch."""
         from vgpu.ops import decode as D, fp8 as Q, prefill as P
-        Q.check_llama_fp8_prefill(self, tokens, kv_caches, start)
+        D.check_llama(self, tokens, kv_caches, start, prefill=True, fp8=True)
         cfg = self.cfg
         B = tokens.shape[0]
-        largest = max([q.codes.numel() for l in self.layers for q in (l.wqkv, l.wo, l.w13, l.w2)]
+        largest = max([getattr(l, name).codes.numel() for l in self.layers for name in LINEARS]
                       + [0 if B in D.BATCHES else self.head.codes.numel()])
         scratch = torch.empty(largest, dtype=torch.bfloat16, device=tokens.device)
 

@@ -197,33 +197,65 @@ def gemv(x: torch.Tensor, w: torch.Tensor, y: torch.Tensor) -> None:
     _check(_lib().vgpu_skinny_fwd(_p(x), _p(w), None, _p(y), B, N, K, 0, _stream()), "vgpu_skinny_fwd")
 
 
-def check_llama_decode(model, tokens: torch.Tensor, kv_caches, pos: torch.Tensor) -> None:
-    """Everything Llama.decode_native needs of its arguments and weights."""
+def check_llama(model, tokens: torch.Tensor, kv_caches, at, *, prefill: bool, fp8: bool) -> None:
+    """Everything decode_native and prefill_native of Llama and LlamaFp8 need
+    of their arguments and weights.  prefill: `at` is `start`, a host int, and
+    tokens are [B, S]; otherwise `at` is `pos`, a 1-element int64 tensor, and
+    tokens are [B, 1].  fp8: the weights are LlamaFp8's buffers, typed by
+    suffix; otherwise bf16 parameters.  Reasons come in one order: shapes,
+    then layout and dtype of caches, weights and `at`, devices last."""
+    from vgpu.ops import fp8 as Q, prefill as P  # both import this module
     cfg = model.cfg
-    if tokens.dim() != 2 or tokens.shape[1] != 1:
+    if prefill and (tokens.dim() != 2 or tokens.shape[1] < 1):
+        raise ValueError(f"tokens: shape {tuple(tokens.shape)}, expected [B, S] with S >= 1")
+    if not prefill and (tokens.dim() != 2 or tokens.shape[1] != 1):
         raise ValueError(f"tokens: shape {tuple(tokens.shape)}, expected [B, 1]")
-    B = tokens.shape[0]
+    B, S = tokens.shape
     hd = cfg.dim // cfg.heads
     if len(kv_caches) != cfg.layers:
         raise ValueError(f"kv_caches: {len(kv_caches)} layers, expected {cfg.layers}")
     if cfg.layers and kv_caches[0][0].dim() != 4:
         raise ValueError(f"kv cache: shape {tuple(kv_caches[0][0].shape)}, expected [B, KVH, ctx, hd]")
-    ctx = kv_caches[0][0].shape[2] if cfg.layers else 1
-    _want_shape(B, cfg.heads, cfg.kv_heads, hd, ctx)
-    if cfg.dim % 8 or cfg.ffn % 8 or cfg.vocab % 4:
+    if prefill:
+        ctx = kv_caches[0][0].shape[2] if cfg.layers else P._want_start(at) + S
+        widths = {"dim": cfg.dim, "ffn": cfg.ffn, "qkv width": (cfg.heads + 2 * cfg.kv_heads) * hd, "vocab": cfg.vocab}
+        for name, v in widths.items():
+            if v < 64 or v % 64:
+                raise ValueError(f"prefill shape not supported: {name} {v} not a multiple of 64")
+        P._want_shape(B, S, P._want_start(at), cfg.heads, cfg.kv_heads, hd, ctx)
+        if at + S > cfg.max_seq:
+            raise ValueError(f"start {at} + {S} tokens > max_seq {cfg.max_seq} of the rope tables")
+        for K, N in ((cfg.dim, widths["qkv width"]), (cfg.dim, 2 * cfg.ffn), (cfg.ffn, cfg.dim)):
+            why = P.gemm_reason(B * S, K, N)
+            if why:
+                raise ValueError(f"prefill shape not supported: {why}")
+    else:
+        ctx = kv_caches[0][0].shape[2] if cfg.layers else 1
+        _want_shape(B, cfg.heads, cfg.kv_heads, hd, ctx)
+    if fp8:
+        Q.check_llama_fp8_config(cfg)
+    elif not prefill and (cfg.dim % 8 or cfg.ffn % 8 or cfg.vocab % 4):
         raise ValueError(f"decode shape not supported: dim {cfg.dim} / ffn {cfg.ffn} not multiples of 8, or vocab "
                          f"{cfg.vocab} not a multiple of 4")
     for i, (kc, vc) in enumerate(kv_caches):
         _want(kc, f"k cache of layer {i}", (B, cfg.kv_heads, ctx, hd), device=False)
         _want(vc, f"v cache of layer {i}", (B, cfg.kv_heads, ctx, hd), device=False)
-    for name, p_ in model.named_parameters():
-        if not p_.is_contiguous():
-            raise ValueError(f"{name}: not contiguous")
-        if p_.dtype != BF16:
-            raise ValueError(f"{name}: dtype {p_.dtype}, expected {BF16}")
-    _want(pos, "pos", (1,), torch.int64, device=False)
-    on = [("tokens", tokens), ("pos", pos)] + [(f"kv cache of layer {i}", t) for i, kv in enumerate(kv_caches)
-                                                for t in kv] + list(model.named_parameters())
+    if fp8:
+        weights = Q._check_buffers(model)
+    else:
+        weights = list(model.named_parameters())
+        for name, p_ in weights:
+            if not p_.is_contiguous():
+                raise ValueError(f"{name}: not contiguous")
+            if p_.dtype != BF16:
+                raise ValueError(f"{name}: dtype {p_.dtype}, expected {BF16}")
+    if prefill:
+        if tokens.dtype != torch.int64:
+            raise ValueError(f"tokens: dtype {tokens.dtype}, expected {torch.int64}")
+    else:
+        _want(at, "pos", (1,), torch.int64, device=False)
+    on = [("tokens", tokens)] + ([] if prefill else [("pos", at)])
+    on += [(f"kv cache of layer {i}", t) for i, kv in enumerate(kv_caches) for t in kv] + weights
     for name, t in on:
         if not t.is_cuda:
             raise ValueError(f"{name}: on {t.device}, expected a GPU tensor")

@@ -20,7 +20,6 @@ import ctypes
 import torch
 
 from vgpu.native import load_kernels
-from vgpu.ops import decode as D
 from vgpu.ops import prefill as P
 from vgpu.ops.decode import BATCHES, BF16, _p, _stream
 from vgpu.ops.prefill import _want_all
@@ -158,7 +157,7 @@ def dequant(codes: torch.Tensor, scale: torch.Tensor, out: torch.Tensor) -> None
 # ---- LlamaFp8's arguments ----------------------------------------------------------------
 
 def check_llama_fp8_config(cfg) -> None:
-    """What the fp8 GEMV asks of a Llama's widths (from_llama and both steps)."""
+    """What the fp8 GEMV asks of a Llama's widths (from_llama, and decode.check_llama for both steps)."""
     hd = cfg.dim // cfg.heads
     widths = {"dim": cfg.dim, "ffn": cfg.ffn, "attention width": cfg.heads * hd}
     for name, v in widths.items():
@@ -181,66 +180,3 @@ def _check_buffers(model) -> list:
             raise ValueError(f"{name}: dtype {t.dtype}, expected {want}")
     return named
 
-
-def _on_gpu(named) -> None:
-    for name, t in named:
-        if not t.is_cuda:
-            raise ValueError(f"{name}: on {t.device}, expected a GPU tensor")
-
-
-def check_llama_fp8_decode(model, tokens: torch.Tensor, kv_caches, pos: torch.Tensor) -> None:
-    """Everything LlamaFp8.decode_native needs of its arguments and buffers."""
-    cfg = model.cfg
-    if tokens.dim() != 2 or tokens.shape[1] != 1:
-        raise ValueError(f"tokens: shape {tuple(tokens.shape)}, expected [B, 1]")
-    B = tokens.shape[0]
-    hd = cfg.dim // cfg.heads
-    if len(kv_caches) != cfg.layers:
-        raise ValueError(f"kv_caches: {len(kv_caches)} layers, expected {cfg.layers}")
-    if cfg.layers and kv_caches[0][0].dim() != 4:
-        raise ValueError(f"kv cache: shape {tuple(kv_caches[0][0].shape)}, expected [B, KVH, ctx, hd]")
-    ctx = kv_caches[0][0].shape[2] if cfg.layers else 1
-    D._want_shape(B, cfg.heads, cfg.kv_heads, hd, ctx)
-    check_llama_fp8_config(cfg)
-    for i, (kc, vc) in enumerate(kv_caches):
-        D._want(kc, f"k cache of layer {i}", (B, cfg.kv_heads, ctx, hd), device=False)
-        D._want(vc, f"v cache of layer {i}", (B, cfg.kv_heads, ctx, hd), device=False)
-    named = _check_buffers(model)
-    D._want(pos, "pos", (1,), torch.int64, device=False)
-    _on_gpu([("tokens", tokens), ("pos", pos)]
-            + [(f"kv cache of layer {i}", t) for i, kv in enumerate(kv_caches) for t in kv] + named)
-
-
-def check_llama_fp8_prefill(model, tokens: torch.Tensor, kv_caches, start: int) -> None:
-    """Everything LlamaFp8.prefill_native needs: what Llama.prefill_native
-    demands of shapes and caches, and the fp8 model's own buffers."""
-    cfg = model.cfg
-    if tokens.dim() != 2 or tokens.shape[1] < 1:
-        raise ValueError(f"tokens: shape {tuple(tokens.shape)}, expected [B, S] with S >= 1")
-    B, S = tokens.shape
-    hd = cfg.dim // cfg.heads
-    if len(kv_caches) != cfg.layers:
-        raise ValueError(f"kv_caches: {len(kv_caches)} layers, expected {cfg.layers}")
-    if cfg.layers and kv_caches[0][0].dim() != 4:
-        raise ValueError(f"kv cache: shape {tuple(kv_caches[0][0].shape)}, expected [B, KVH, ctx, hd]")
-    ctx = kv_caches[0][0].shape[2] if cfg.layers else P._want_start(start) + S
-    widths = {"dim": cfg.dim, "ffn": cfg.ffn, "qkv width": (cfg.heads + 2 * cfg.kv_heads) * hd, "vocab": cfg.vocab}
-    for name, v in widths.items():
-        if v < 64 or v % 64:
-            raise ValueError(f"prefill shape not supported: {name} {v} not a multiple of 64")
-    P._want_shape(B, S, P._want_start(start), cfg.heads, cfg.kv_heads, hd, ctx)
-    if start + S > cfg.max_seq:
-        raise ValueError(f"start {start} + {S} tokens > max_seq {cfg.max_seq} of the rope tables")
-    for K, N in ((cfg.dim, widths["qkv width"]), (cfg.dim, 2 * cfg.ffn), (cfg.ffn, cfg.dim)):
-        why = P.gemm_reason(B * S, K, N)
-        if why:
-            raise ValueError(f"prefill shape not supported: {why}")
-    check_llama_fp8_config(cfg)
-    for i, (kc, vc) in enumerate(kv_caches):
-        D._want(kc, f"k cache of layer {i}", (B, cfg.kv_heads, ctx, hd), device=False)
-        D._want(vc, f"v cache of layer {i}", (B, cfg.kv_heads, ctx, hd), device=False)
-    named = _check_buffers(model)
-    if tokens.dtype != torch.int64:
-        raise ValueError(f"tokens: dtype {tokens.dtype}, expected {torch.int64}")
-    _on_gpu([("tokens", tokens)] + [(f"kv cache of layer {i}", t) for i, kv in enumerate(kv_caches) for t in kv]
-            + named)

@@ -177,42 +177,3 @@ def gemm(x: torch.Tensor, w: torch.Tensor, y: torch.Tensor) -> None:
     _check(lib.vgpu_conv2d_nhwc_ws(_p(x), _p(w), _p(y), None, None, None, None, 1, M, 1, K, N, 1, 1, 0, 0, _p(ws),
                                    need, _stream()), "vgpu_conv2d_nhwc_ws")
 
-
-def check_llama_prefill(model, tokens: torch.Tensor, kv_caches, start: int) -> None:
-    """Everything Llama.prefill_native needs of its arguments and weights."""
-    cfg = model.cfg
-    if tokens.dim() != 2 or tokens.shape[1] < 1:
-        raise ValueError(f"tokens: shape {tuple(tokens.shape)}, expected [B, S] with S >= 1")
-    B, S = tokens.shape
-    hd = cfg.dim // cfg.heads
-    if len(kv_caches) != cfg.layers:
-        raise ValueError(f"kv_caches: {len(kv_caches)} layers, expected {cfg.layers}")
-    if cfg.layers and kv_caches[0][0].dim() != 4:
-        raise ValueError(f"kv cache: shape {tuple(kv_caches[0][0].shape)}, expected [B, KVH, ctx, hd]")
-    ctx = kv_caches[0][0].shape[2] if cfg.layers else _want_start(start) + S
-    widths = {"dim": cfg.dim, "ffn": cfg.ffn, "qkv width": (cfg.heads + 2 * cfg.kv_heads) * hd, "vocab": cfg.vocab}
-    for name, v in widths.items():
-        if v < 64 or v % 64:
-            raise ValueError(f"prefill shape not supported: {name} {v} not a multiple of 64")
-    _want_shape(B, S, _want_start(start), cfg.heads, cfg.kv_heads, hd, ctx)
-    if start + S > cfg.max_seq:
-        raise ValueError(f"start {start} + {S} tokens > max_seq {cfg.max_seq} of the rope tables")
-    for K, N in ((cfg.dim, widths["qkv width"]), (cfg.dim, 2 * cfg.ffn), (cfg.ffn, cfg.dim)):
-        why = gemm_reason(B * S, K, N)
-        if why:
-            raise ValueError(f"prefill shape not supported: {why}")
-    for i, (kc, vc) in enumerate(kv_caches):
-        _want(kc, f"k cache of layer {i}", (B, cfg.kv_heads, ctx, hd), device=False)
-        _want(vc, f"v cache of layer {i}", (B, cfg.kv_heads, ctx, hd), device=False)
-    for name, p_ in model.named_parameters():
-        if not p_.is_contiguous():
-            raise ValueError(f"{name}: not contiguous")
-        if p_.dtype != BF16:
-            raise ValueError(f"{name}: dtype {p_.dtype}, expected {BF16}")
-    if tokens.dtype != torch.int64:
-        raise ValueError(f"tokens: dtype {tokens.dtype}, expected {torch.int64}")
-    on = [("tokens", tokens)] + [(f"kv cache of layer {i}", t) for i, kv in enumerate(kv_caches) for t in kv]
-    on += list(model.named_parameters())
-    for name, t in on:
-        if not t.is_cuda:
-            raise ValueError(f"{name}: on {t.device}, expected a GPU tensor")
